@@ -29,7 +29,7 @@ SOURCES = HOST_SOURCES + [p for v in PROGRAMS.values() for p in v]
 SANITIZE = "-fsanitize=address,undefined,float-cast-overflow"
 FLAGS = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", SANITIZE, "-fno-sanitize-recover=undefined,float-cast-overflow",
          "-I", os.path.join(ROOT, "include"), "-I", HOST]
-FONT_DIRS = ["/usr/share/fonts/truetype/dejavu", "/root/reference/smelter-render/fonts"]
+FONT_DIRS = ["/usr/share/fonts/truetype/dejavu", os.path.join(HERE, "golden", "fonts")]
 
 
 def _newest_dependency():

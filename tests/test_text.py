@@ -10,12 +10,12 @@ from smelter_amd import _ffi
 from tests import text_twin as T
 from smelter_amd.scene import Scene, SceneError
 
-REF_FONTS = "/root/reference/smelter-render/fonts"          # Inter, bundled by the reference (only in the build container)
+INTER_FONTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fonts")   # the reference's Inter, subset (gen_font_fixtures.py)
 SYS_FONTS = "/usr/share/fonts/truetype/dejavu"              # part of the image, on the GPU box too
 
 
 def _book():
-    for d in (REF_FONTS, SYS_FONTS):
+    for d in (INTER_FONTS, SYS_FONTS):
         if os.path.isdir(d):
             return T.FontBook.from_dir(d)
     pytest.skip("no TrueType fonts on this machine")
@@ -144,9 +144,7 @@ def test_glyph_run_fits_the_node_and_the_atlas():
 def test_pair_kerning_comes_from_the_gpos_kern_feature():
     """rustybuzz applies the font's `kern` feature under Shaping::Advanced: Inter tucks V under A and o under T; pairs without an
     entry keep their advances; the adjustment is in font units and scales with the size."""
-    if not os.path.isdir(REF_FONTS):
-        pytest.skip("needs the reference's bundled Inter")
-    font = T.FontBook.from_dir(REF_FONTS).match("Inter 18pt")
+    font = T.FontBook.from_dir(INTER_FONTS).match("Inter 18pt")
     g = font.glyph_name
     assert font.kerning(g("A"), g("V")) < -50 and font.kerning(g("T"), g("o")) < -50
     assert font.kerning(g("a"), g("b")) == 0.0 and font.kerning(g("o"), g("o")) == 0.0

@@ -14,12 +14,12 @@ from smelter_amd import _ffi
 from tests import text_twin as T
 from smelter_amd.scene import Scene
 
-REF_FONTS = "/root/reference/smelter-render/fonts"          # Inter, bundled by the reference (only in the build container)
+INTER_FONTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fonts")   # the reference's Inter, subset (gen_font_fixtures.py)
 SYS_FONTS = "/usr/share/fonts/truetype/dejavu"              # part of the image, on the GPU box too
-FONT_DIRS = [d for d in (REF_FONTS, SYS_FONTS) if os.path.isdir(d)]
+FONT_DIRS = [d for d in (INTER_FONTS, SYS_FONTS) if os.path.isdir(d)]
 
 
-@pytest.fixture(scope="module", params=FONT_DIRS or [None])
+@pytest.fixture(scope="module", params=FONT_DIRS or [None], ids=lambda d: "golden-inter" if d == INTER_FONTS else d)
 def books(request):
     if request.param is None:
         pytest.skip("no TrueType fonts on this machine")
@@ -27,7 +27,7 @@ def books(request):
     n = native.add_dir(request.param)
     py = T.FontBook.from_dir(request.param)
     assert n == len(py.fonts) == len(native)
-    yield native, py, ("Inter 18pt" if request.param == REF_FONTS else "DejaVu Sans")
+    yield native, py, ("Inter 18pt" if request.param == INTER_FONTS else "DejaVu Sans")
     native.close()
 
 
