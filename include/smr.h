@@ -234,7 +234,8 @@ typedef enum smr_kernel_id {
     SMR_KERNEL_FRAME_TO_RGBA = 5,    /* the input converters (InputTexture::convert_to_node_texture): launches — a block-converter launch takes up to 16 frames */
     SMR_KERNEL_COMPOSE_OUTPUT = 6,   /* k_compose_output: layout shader + output conversion */
     SMR_KERNEL_APPLY_LAYOUTS = 7,    /* k_apply_layouts: the general compositor */
-    SMR_KERNEL_COUNT_ = 8
+    SMR_KERNEL_MOVE_RECTS = 8,       /* k_move_rects: the local gather's transport (smr_gather_tiles), one launch per sending context and 16 rectangles */
+    SMR_KERNEL_COUNT_ = 9
 } smr_kernel_id;
 SMR_API int smr_debug_kernel_launches(const smr_ctx *ctx, uint32_t kernel, uint64_t *count);
 
@@ -559,6 +560,21 @@ SMR_API int smr_renderer_render(smr_renderer *r, int64_t pts_ns, const smr_input
  * one pts sequence, transitions identical to the single-lane renderer.  Each lane keeps its own pair of output frames and node
  * surfaces; smr_output_frame.ctx says which context produced a frame.  smr_renderer_sync waits for every lane. */
 SMR_API int smr_renderer_add_lane(smr_renderer *r, smr_ctx *ctx);
+/* Inputs sharded over several contexts — usually one per device — behind the one renderer (the library's scaling axis beyond a single
+ * GPU: SURVEY.md section 8e).  Per layout node and frame every remote input that exactly one texture layout resamples becomes its dst-sized
+ * tile on the context that owns it (smr_ingest_resample_batch, one call per owner), the tiles are gathered on the renderer's own context
+ * (smr_gather_tiles over a local communicator the renderer creates: one k_move_rects launch per owner) and composed there; an input that
+ * does not fit that rule (1:1, sampled twice, a Shader node's child, the output's root, SMR_MODE_CPU_OPTIMIZED) has its raw planes moved
+ * to a root-resident frame by the same gather.  Every scene renders to the bytes the single-context renderer produces; smr_renderer_render
+ * keeps its meaning (the frame of THIS pts, nothing blocks the host, smr_output_frame.ctx is the renderer's own context) and
+ * smr_renderer_sync also waits for the shards.  Contexts on the root's own device get SMR_OPT_SHARED_DEVICE.
+ * Lanes and shards do not combine: smr_renderer_add_shard on a renderer with lanes and smr_renderer_add_lane on one with shards fail. */
+/* A further context (usually another device) that takes a share of the renderer's inputs.  Call before the first
+ * smr_renderer_register_input.  Same rendering mode as the renderer's context, else refused. */
+SMR_API int smr_renderer_add_shard(smr_renderer *r, smr_ctx *ctx);
+/* The context an input's frames must be resident on (smr_frame_create / upload / wrap there).  k-th registered input ->
+ * context k mod N of {the renderer's own, shards in the order added}; fixed until the input is unregistered. */
+SMR_API int smr_renderer_input_ctx(smr_renderer *r, const char *input_id, smr_ctx **out);
 SMR_API int smr_renderer_sync(smr_renderer *r);
 
 /* ABI version: a host checks smr_abi_version() == SMR_ABI_VERSION when it loads the library.
@@ -568,6 +584,8 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      SMR_KERNEL_INGEST_MFMA_WG, counts SMR_KERNEL_FRAME_TO_RGBA_420.  smr_text_params moved in front of the font-book entry points.  The
  *      SMR_CONVERT_GENERAL / SMR_DISABLE_FUSED / SMR_COMPOSE_SELECT environment knobs are smr_ctx_set_option options in a product build
  *      (the environment is read by laboratory builds only).
+ *      Added since, without a new version (additions only: nothing a version-2 host calls changed): SMR_KERNEL_MOVE_RECTS (counter slot 8),
+ *      smr_renderer_add_shard, smr_renderer_input_ctx.
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

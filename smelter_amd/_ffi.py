@@ -42,7 +42,7 @@ EXPORTS = [
     "smr_renderer_create", "smr_renderer_destroy", "smr_renderer_last_error", "smr_renderer_register_input",
     "smr_renderer_unregister_input", "smr_renderer_register_image", "smr_renderer_register_shader", "smr_renderer_update_scene",
     "smr_renderer_unregister_output", "smr_renderer_node_count", "smr_renderer_node_info", "smr_renderer_set_text", "smr_renderer_set_text_measurer",
-    "smr_renderer_render", "smr_renderer_add_lane", "smr_renderer_sync",
+    "smr_renderer_render", "smr_renderer_add_lane", "smr_renderer_sync", "smr_renderer_add_shard", "smr_renderer_input_ctx",
     "smr_comm_create_local", "smr_comm_unique_id", "smr_comm_create_rank", "smr_comm_destroy", "smr_comm_world", "smr_comm_rank",
     "smr_comm_last_error", "smr_gather_tiles",
     "smr_fontbook_create", "smr_fontbook_destroy", "smr_fontbook_last_error", "smr_fontbook_add_file", "smr_fontbook_add_memory",
@@ -230,6 +230,8 @@ def load():
         "smr_renderer_render": ([P, C.c_int64, C.POINTER(InputFrame), U, C.POINTER(OutputFrame), U, C.POINTER(U)], I),
         "smr_renderer_add_lane": ([P, P], I),
         "smr_renderer_sync": ([P], I),
+        "smr_renderer_add_shard": ([P, P], I),
+        "smr_renderer_input_ctx": ([P, C.c_char_p, PP], I),
         "smr_fontbook_create": ([PP], I),
         "smr_fontbook_destroy": ([P], None),
         "smr_fontbook_last_error": ([P], C.c_char_p),

@@ -4,6 +4,14 @@
 // walk of every output's render graph (render_graph.rs, node.rs:22-181) — input refs, images, text, shader nodes, nested
 // layout nodes into RGBA8 node surfaces — and read_outputs (render_loop.rs:59-230) fused into the root layout node's launch.
 // SURVEY.md §8 a14 (+ a2, a4); no GPU code here, only calls into the C ABI of this library.
+//
+// Sharded renderer (smr_renderer_add_shard): inputs are dealt to several contexts, usually one per device.  Per layout node and frame every
+// remote input that exactly one texture layout resamples is turned into its dst-sized tile ON ITS OWNER (smr_ingest_resample_batch, one call
+// per owner), the tiles travel to the root in one smr_gather_tiles (k_move_rects: one launch per owner) and the root's smr_render_layouts
+// samples the tile where a single context would have made it itself — the same bytes.  Whatever does not fit that rule (a 1:1 input, one
+// sampled twice, a Shader node's child, the output's root, SMR_MODE_CPU_OPTIMIZED) has its raw planes moved to a root-resident frame by the
+// same gather and is rendered exactly as on one context.
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <map>
@@ -12,6 +20,16 @@
 #include "scene.h"
 
 using namespace smr_host;
+
+// The entry points only a sharded renderer calls are weak references: the host half also links without the GPU half (tests/san runs this file
+// against a stand-in device under the sanitizers); smr_renderer_add_shard refuses there.
+#pragma weak smr_comm_create_local
+#pragma weak smr_comm_destroy
+#pragma weak smr_comm_last_error
+#pragma weak smr_gather_tiles
+#pragma weak smr_ingest_resample_batch
+#pragma weak smr_resample_plan_make
+extern "C" int smr_ctx_device_index(const smr_ctx *ctx) __attribute__((weak));  // smr_ctx.hip; not part of the ABI
 
 namespace {
 
@@ -26,6 +44,8 @@ struct Source {
     const smr_surface *surface = nullptr;
     const smr_frame *frame = nullptr;
     uint32_t w = 0, h = 0;
+    uint32_t owner = 0;   // SMR_SOURCE_FRAME: index of the context the frame is resident on (0 = the renderer's own)
+    int node = -1;        // ... and the graph node of its InputStream component (the key of its tile / staging slots)
     bool opaque = false;  // every texel's alpha is 255 (the renderer writes its node surfaces itself, so it may know): the compositor then copies
                           // or samples the layer where it would otherwise blend it (SMR_SOURCE_OPAQUE_SURFACE) — the same bytes, fewer of them touched
 };
@@ -62,7 +82,17 @@ bool layouts_leave_an_opaque_surface(const std::vector<smr_layout> &layouts, con
 // What one frame in flight owns of an output: its two alternating output frames and the per-node intermediate surfaces.
 // (One lane = the reference's renderer; with more lanes consecutive frames are enqueued on different contexts / HIP streams
 // and overlap on the device, while the scene — and with it every transition — stays one state advanced by one pts sequence.)
+// What a remote InputStream node owns of one of the two alternating sets (an owner may resample frame k + 1 while the root composes frame k)
+struct ShardSlot {
+    smr_surface *tile_src = nullptr;  // the dst-sized tile where the owner resamples it
+    smr_ctx *tile_ctx = nullptr;      // ... and the owner's context
+    smr_surface *tile_dst = nullptr;  // the same tile on the root
+    smr_frame staged = {};            // fallback: a root-resident frame of the input's own format and size
+    bool have_staged = false;
+};
+
 struct OutputLane {
+    std::vector<ShardSlot> shard[2];           // per graph node, sharded renderers only; the set of a frame is the output's `flip`
     smr_frame frames[2];
     bool have_frames = false;
     int flip = 0;
@@ -83,6 +113,10 @@ struct Output {
 struct smr_renderer {
     smr_ctx *ctx = nullptr;           // the context GPU work is issued on: lane_ctx[0] outside smr_renderer_render, the frame's lane inside
     std::vector<smr_ctx *> lane_ctx;  // [0] = the context given to smr_renderer_create, then smr_renderer_add_lane's
+    std::vector<smr_ctx *> shard_ctx; // sharded: [0] = lane_ctx[0], then smr_renderer_add_shard's; empty otherwise
+    smr_comm *comm = nullptr;         // local communicator over shard_ctx (root = 0), rebuilt when a shard is added
+    std::map<std::string, uint32_t> input_owner;  // input_id -> index into shard_ctx (0 while not sharded)
+    uint64_t registrations = 0;       // the k of "k-th registered input -> context k mod N"
     uint64_t frame_no = 0;
     int64_t timeout_ns = 500000000;  // stream_fallback_timeout
     std::set<std::string> inputs;
@@ -114,6 +148,18 @@ void free_surfaces(smr_renderer *r, std::vector<smr_surface *> &v) {
 }
 void sync_lanes(smr_renderer *r) {
     for (smr_ctx *c : r->lane_ctx) smr_sync(c);
+    for (size_t i = 1; i < r->shard_ctx.size(); i++) smr_sync(r->shard_ctx[i]);
+}
+// (callers have synchronised every context: sync_lanes)
+void free_shard_slots(smr_renderer *r, OutputLane &l) {
+    for (auto &set : l.shard) {
+        for (ShardSlot &s : set) {
+            if (s.tile_src) smr_surface_destroy(s.tile_ctx, s.tile_src);
+            if (s.tile_dst) smr_surface_destroy(r->lane_ctx[0], s.tile_dst);
+            if (s.have_staged) smr_frame_destroy(r->lane_ctx[0], &s.staged);
+        }
+        set.clear();
+    }
 }
 void free_lane_frames(smr_renderer *r, OutputLane &l) {
     if (!l.have_frames) return;
@@ -127,6 +173,7 @@ void free_node_surfaces(smr_renderer *r, Output &o) {
     for (OutputLane &l : o.lanes) {
         free_surfaces(r, l.node_surface);
         free_surfaces(r, l.scaled_image);
+        free_shard_slots(r, l);
         l.node_surface.assign(n, nullptr);
         l.scaled_image.assign(n, nullptr);
     }
@@ -144,6 +191,7 @@ int enter_lane(smr_renderer *r, Output &o, size_t lane) {
     o.l = &l;
     const size_t n = o.scene.nodes().size();
     if (l.node_surface.size() != n) { l.node_surface.assign(n, nullptr); l.scaled_image.assign(n, nullptr); }
+    if (r->shard_ctx.size() > 1 && l.shard[0].size() != n) { l.shard[0].assign(n, ShardSlot()); l.shard[1].assign(n, ShardSlot()); }
     if (!l.have_frames) {
         int rc = gpu(r, smr_frame_create(r->ctx, o.format, o.w, o.h, &l.frames[0]), "output frame");
         if (rc < 0) return rc;
@@ -163,6 +211,131 @@ int ensure_surface(smr_renderer *r, smr_surface *&slot, uint32_t w, uint32_t h) 
     if (slot && smr_surface_info_get(slot, &info) == 0 && info.width == w && info.height == h) return 0;
     if (slot) { smr_surface_destroy(r->ctx, slot); slot = nullptr; }
     return gpu(r, smr_surface_create(r->ctx, w, h, SMR_PX_RGBA8, &slot), "node surface");
+}
+
+// ---- sharded renderers
+bool sharded(const smr_renderer *r) { return r->shard_ctx.size() > 1; }
+int shard_gpu(smr_renderer *r, smr_ctx *c, int rc, const char *what) {
+    if (rc >= 0) return rc;
+    return fail(r, rc, std::string(what) + ": " + smr_last_error(c));
+}
+struct Gather {  // what one smr_gather_tiles call moves
+    std::vector<uint32_t> owner;
+    std::vector<const smr_surface *> src;
+    std::vector<smr_surface *> dst;
+};
+int run_gather(smr_renderer *r, Gather &g) {
+    if (g.owner.empty()) return 0;
+    const int rc = smr_gather_tiles(r->comm, 0, g.owner.data(), g.src.data(), g.dst.data(), (uint32_t)g.owner.size());
+    if (rc < 0) return fail(r, rc, std::string("shard gather: ") + smr_comm_last_error(r->comm));
+    return 0;
+}
+// The root-resident stand-in of a remote frame: same format and size, its planes queued on `g`.  `s` then names the stand-in.
+int stage_remote_frame(smr_renderer *r, Output &o, Source &s, Gather &g) {
+    ShardSlot &slot = o.l->shard[o.l->flip][s.node];
+    const smr_frame *f = s.frame;
+    if (slot.have_staged && (slot.staged.format != f->format || slot.staged.width != f->width || slot.staged.height != f->height)) {
+        sync_lanes(r);  // (an owner may still be writing it)
+        smr_frame_destroy(r->lane_ctx[0], &slot.staged);
+        slot.have_staged = false;
+    }
+    if (!slot.have_staged) {
+        int rc = gpu(r, smr_frame_create(r->ctx, f->format, f->width, f->height, &slot.staged), "staged input frame");
+        if (rc < 0) return rc;
+        slot.have_staged = true;
+    }
+    for (int p = 0; p < 3; p++) {
+        if (!f->planes[p] != !slot.staged.planes[p]) return fail(r, -1, "sharded renderer: a remote input frame does not have the planes of its format");
+        if (!f->planes[p]) continue;
+        g.owner.push_back(s.owner); g.src.push_back(f->planes[p]); g.dst.push_back(slot.staged.planes[p]);
+    }
+    s.frame = &slot.staged;
+    s.owner = 0;
+    return 0;
+}
+// ... for one frame outside a layout node (a Shader node's child, the output's root): a gather of its own
+int localize_frame(smr_renderer *r, Output &o, Source &s) {
+    if (!sharded(r) || s.kind != SMR_SOURCE_FRAME || s.owner == 0) return 0;
+    Gather g;
+    int rc = stage_remote_frame(r, o, s, g);
+    if (rc < 0) return rc;
+    return run_gather(r, g);
+}
+int ensure_tile(smr_renderer *r, smr_ctx *ctx, smr_surface *&slot, uint32_t w, uint32_t h) {
+    smr_surface_info info;
+    if (slot && smr_surface_info_get(slot, &info) == 0 && info.width == w && info.height == h) return 0;
+    return shard_gpu(r, ctx, smr_surface_create(ctx, w, h, SMR_PX_RGBA8, &slot), "shard tile");
+}
+// A layout node's remote children, between its layout list (r->layouts) and its smr_render_layouts: tiles where the rule allows, staged
+// frames otherwise, ONE gather.  Rewrites r->layouts (crop = the whole tile) and srcs; kids keep describing the inputs themselves.
+int shard_layout_sources(smr_renderer *r, Output &o, std::vector<Source> &kids, std::vector<smr_source> &srcs) {
+    if (!sharded(r)) return 0;
+    const bool resampler = smr_ctx_mode(r->ctx) == SMR_MODE_GPU_OPTIMIZED;  // CpuOptimized has no resampler (layout/layout_renderer.rs:22-27)
+    Gather g;
+    struct Batch { std::vector<const smr_frame *> in; std::vector<float> crops; std::vector<smr_surface *> dst; };
+    std::vector<Batch> batch(r->shard_ctx.size());
+    for (size_t k = 0; k < kids.size(); k++) {
+        Source &s = kids[k];
+        if (s.kind != SMR_SOURCE_FRAME || s.owner == 0) continue;
+        int uses = 0;
+        smr_layout *L = nullptr;
+        for (smr_layout &l : r->layouts)
+            if (l.type == 0 && l.source_index == k) { uses++; L = &l; }
+        if (uses == 0) { srcs[k].kind = SMR_SOURCE_NONE; srcs[k].frame = nullptr; continue; }  // nothing samples it: nothing to move
+        bool tiled = false;
+        if (uses == 1 && resampler) {
+            // resample_scaled_children (layout.rs:258-261), the rule smr_render_layouts itself applies to a frame source
+            const float rw = roundf(L->width), rh = roundf(L->height);
+            const uint32_t dw = rw >= 1.0f ? (uint32_t)rw : 1u, dh = rh >= 1.0f ? (uint32_t)rh : 1u;
+            smr_resample_plan plan;
+            const int kind = smr_resample_plan_make(s.w, s.h, L->crop, dw, dh, &plan);
+            if (kind > 0 && dw <= 16384 && dh <= 16384) {
+                ShardSlot &slot = o.l->shard[o.l->flip][s.node];
+                smr_ctx *oc = r->shard_ctx[s.owner];
+                smr_surface_info info;
+                const bool fits = slot.tile_src && slot.tile_dst && slot.tile_ctx == oc && smr_surface_info_get(slot.tile_src, &info) == 0 &&
+                                  info.width == dw && info.height == dh;
+                if (!fits) {
+                    if (slot.tile_src || slot.tile_dst) {
+                        sync_lanes(r);  // (the owner may still be sending the old tile, the root composing from it)
+                        if (slot.tile_src) smr_surface_destroy(slot.tile_ctx, slot.tile_src);
+                        if (slot.tile_dst) smr_surface_destroy(r->lane_ctx[0], slot.tile_dst);
+                        slot.tile_src = slot.tile_dst = nullptr;
+                    }
+                    slot.tile_ctx = oc;
+                    int rc = ensure_tile(r, oc, slot.tile_src, dw, dh);
+                    if (rc >= 0) rc = ensure_tile(r, r->ctx, slot.tile_dst, dw, dh);
+                    if (rc < 0) return rc;
+                }
+                Batch &b = batch[s.owner];
+                b.in.push_back(s.frame);
+                b.crops.insert(b.crops.end(), L->crop, L->crop + 4);
+                b.dst.push_back(slot.tile_src);
+                g.owner.push_back(s.owner); g.src.push_back(slot.tile_src); g.dst.push_back(slot.tile_dst);
+                srcs[k].kind = frame_opaque(s.frame) ? (uint32_t)SMR_SOURCE_OPAQUE_SURFACE : (uint32_t)SMR_SOURCE_SURFACE;
+                srcs[k].surface = slot.tile_dst; srcs[k].frame = nullptr;
+                L->crop[0] = 0.0f; L->crop[1] = 0.0f; L->crop[2] = (float)dw; L->crop[3] = (float)dh;
+                tiled = true;
+            }
+        }
+        if (!tiled) {
+            Source staged = s;
+            int rc = stage_remote_frame(r, o, staged, g);
+            if (rc < 0) return rc;
+            srcs[k].frame = staged.frame;
+        }
+    }
+    for (size_t c = 1; c < batch.size(); c++) {
+        Batch &b = batch[c];
+        if (b.in.empty()) continue;
+        std::vector<int> kinds(b.in.size(), 0);
+        int rc = shard_gpu(r, r->shard_ctx[c], smr_ingest_resample_batch(r->shard_ctx[c], b.in.data(), b.crops.data(), b.dst.data(), (uint32_t)b.in.size(), kinds.data()),
+                           "shard ingest");
+        if (rc < 0) return rc;
+        for (int kd : kinds)
+            if (kd <= 0) return fail(r, -3, "sharded renderer: a tile's resample plan changed between planning and ingest");
+    }
+    return run_gather(r, g);
 }
 
 struct FrameSetView {
@@ -197,6 +370,8 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
             const int64_t oldest = fs.pts_ns > r->timeout_ns ? fs.pts_ns - r->timeout_ns : 0;  // Duration::saturating_sub
             if (oldest > f.pts_ns) return 0;
             out.kind = SMR_SOURCE_FRAME; out.frame = f.frame; out.w = f.frame->width; out.h = f.frame->height;
+            out.node = idx;
+            if (sharded(r)) { auto ow = r->input_owner.find(c.ref_id); out.owner = ow == r->input_owner.end() ? 0u : ow->second; }
             return 0;
         }
         return 0;
@@ -246,6 +421,8 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
         std::vector<bool> src_opaque;
         for (size_t k = 0; k < kids.size(); k++) {
             if (kids[k].kind == SMR_SOURCE_FRAME) {
+                rc = localize_frame(r, o, kids[k]);
+                if (rc < 0) return rc;
                 smr_surface *&t = o.l->node_surface[g.children[k]];
                 rc = ensure_surface(r, t, kids[k].w, kids[k].h);
                 if (rc < 0) return rc;
@@ -305,6 +482,8 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
     const bool node_opaque = layouts_leave_an_opaque_surface(r->layouts, kids, w, h);
     int rc = ensure_surface(r, o.l->node_surface[idx], w, h);
     if (rc < 0) return rc;
+    rc = shard_layout_sources(r, o, kids, srcs);
+    if (rc < 0) return rc;
     rc = gpu(r, smr_render_layouts(r->ctx, r->layouts.data(), (uint32_t)r->layouts.size(), srcs.data(), (uint32_t)srcs.size(), w, h, nullptr,
                                    o.l->node_surface[idx]),
              "layout node");
@@ -335,6 +514,10 @@ int render_output(smr_renderer *r, Output &o, const FrameSetView &fs, const smr_
         uint32_t w = 0, h = 0;
         std::string err;
         if (!o.scene.node_layouts(0, fs.pts_ns, res, smr_ctx_mode(r->ctx) == SMR_MODE_GPU_OPTIMIZED, r->layouts, w, h, err)) return fail(r, -1, err);
+        if (w != 0 && h != 0) {
+            int rc = shard_layout_sources(r, o, kids, srcs);
+            if (rc < 0) return rc;
+        }
         if (w == o.w && h == o.h && o.format != SMR_FRAME_RGBA) {
             // LayoutNode::render + read_outputs in one go: the root's RGBA target never exists
             return gpu(r, smr_render_layouts(r->ctx, r->layouts.data(), (uint32_t)r->layouts.size(), srcs.data(), (uint32_t)srcs.size(), w, h,
@@ -360,6 +543,8 @@ int render_output(smr_renderer *r, Output &o, const FrameSetView &fs, const smr_
     int rc = render_node(r, o, 0, fs, s);
     if (rc < 0) return rc;
     if (s.kind == SMR_SOURCE_NONE) return gpu(r, smr_frame_fill_black(r->ctx, target), "empty output");  // render_loop.rs:127-139
+    rc = localize_frame(r, o, s);
+    if (rc < 0) return rc;
     const smr_surface *rgba = s.surface;
     if (s.kind == SMR_SOURCE_FRAME) {
         rc = ensure_surface(r, o.l->node_surface[0], s.w, s.h);
@@ -400,6 +585,7 @@ SMR_API void smr_renderer_destroy(smr_renderer *r) {
     for (auto &kv : r->outputs) free_output(r, kv.second);
     for (auto &kv : r->images)
         if (kv.second.surface) smr_surface_destroy(r->ctx, kv.second.surface);
+    if (r->comm) smr_comm_destroy(r->comm);
     delete r;
 }
 
@@ -407,12 +593,16 @@ SMR_API const char *smr_renderer_last_error(const smr_renderer *r) { return r ? 
 
 SMR_API int smr_renderer_register_input(smr_renderer *r, const char *input_id) {
     if (!r || !input_id) return fail(r, -1, "smr_renderer_register_input: null argument");
-    r->inputs.insert(input_id);
+    if (r->inputs.insert(input_id).second) {
+        const uint64_t k = r->registrations++;
+        r->input_owner[input_id] = sharded(r) ? (uint32_t)(k % r->shard_ctx.size()) : 0u;
+    }
     return 0;
 }
 SMR_API int smr_renderer_unregister_input(smr_renderer *r, const char *input_id) {
     if (!r || !input_id) return fail(r, -1, "smr_renderer_unregister_input: null argument");
     r->inputs.erase(input_id);
+    r->input_owner.erase(input_id);
     return 0;
 }
 
@@ -662,9 +852,53 @@ SMR_API int smr_renderer_add_lane(smr_renderer *r, smr_ctx *ctx) {
     for (smr_ctx *c : r->lane_ctx)
         if (c == ctx) return fail(r, -1, "smr_renderer_add_lane: this context is a lane already");
     if (smr_ctx_mode(ctx) != smr_ctx_mode(r->ctx)) return fail(r, -1, "smr_renderer_add_lane: the lane's context has another rendering mode");
+    if (sharded(r)) return fail(r, -1, "smr_renderer_add_lane: this renderer has shards; lanes and shards do not combine");
     r->lane_ctx.push_back(ctx);
     // frames in flight: every lane's kernels run beside another lane's from now on
     for (smr_ctx *c : r->lane_ctx) (void)smr_ctx_set_option(c, SMR_OPT_SHARED_DEVICE, 1);
+    return 0;
+}
+
+SMR_API int smr_renderer_add_shard(smr_renderer *r, smr_ctx *ctx) {
+    if (!r || !ctx) return fail(r, -1, "smr_renderer_add_shard: null argument");
+    if (!smr_comm_create_local || !smr_comm_destroy || !smr_comm_last_error || !smr_gather_tiles || !smr_ingest_resample_batch || !smr_resample_plan_make)
+        return fail(r, -1, "smr_renderer_add_shard: this build of the renderer has no device half");
+    if (r->lane_ctx.size() > 1) return fail(r, -1, "smr_renderer_add_shard: this renderer has lanes; lanes and shards do not combine");
+    if (r->registrations) return fail(r, -1, "smr_renderer_add_shard: call it before the first smr_renderer_register_input");
+    if (ctx == r->lane_ctx[0]) return fail(r, -1, "smr_renderer_add_shard: this context is the renderer's own");
+    for (smr_ctx *c : r->shard_ctx)
+        if (c == ctx) return fail(r, -1, "smr_renderer_add_shard: this context is a shard already");
+    if (smr_ctx_mode(ctx) != smr_ctx_mode(r->ctx)) return fail(r, -1, "smr_renderer_add_shard: the shard's context has another rendering mode");
+    std::vector<smr_ctx *> all = r->shard_ctx;
+    if (all.empty()) all.push_back(r->lane_ctx[0]);
+    all.push_back(ctx);
+    smr_comm *comm = nullptr;
+    const int rc = smr_comm_create_local(all.data(), (uint32_t)all.size(), &comm);
+    if (rc < 0) {
+        const char *a = smr_last_error(ctx), *b = smr_last_error(r->ctx);
+        return fail(r, rc, std::string("smr_renderer_add_shard: ") + (a && *a ? a : b && *b ? b : "the contexts cannot form a local communicator"));
+    }
+    sync_lanes(r);  // (outputs rendered so far: their per-node sets gain the shard slots at the next frame)
+    if (r->comm) smr_comm_destroy(r->comm);
+    r->comm = comm;
+    r->shard_ctx = all;
+    // contexts that share the root's device run their kernels beside the root's from now on (as smr_renderer_add_lane's do)
+    if (smr_ctx_device_index) {
+        const int root_dev = smr_ctx_device_index(r->lane_ctx[0]);
+        bool shared = false;
+        for (size_t i = 1; i < all.size(); i++)
+            if (smr_ctx_device_index(all[i]) == root_dev) { (void)smr_ctx_set_option(all[i], SMR_OPT_SHARED_DEVICE, 1); shared = true; }
+        if (shared) (void)smr_ctx_set_option(r->lane_ctx[0], SMR_OPT_SHARED_DEVICE, 1);
+    }
+    return 0;
+}
+
+SMR_API int smr_renderer_input_ctx(smr_renderer *r, const char *input_id, smr_ctx **out) {
+    if (!r || !input_id || !out) return fail(r, -1, "smr_renderer_input_ctx: null argument");
+    *out = nullptr;
+    auto it = r->input_owner.find(input_id);
+    if (it == r->input_owner.end()) return fail(r, -1, std::string("smr_renderer_input_ctx: input \"") + input_id + "\" is not registered");
+    *out = sharded(r) ? r->shard_ctx[it->second] : r->lane_ctx[0];
     return 0;
 }
 
@@ -674,6 +908,10 @@ SMR_API int smr_renderer_sync(smr_renderer *r) {
     for (smr_ctx *c : r->lane_ctx) {
         const int e = smr_sync(c);
         if (e < 0 && rc >= 0) rc = gpu(r, e, "sync");
+    }
+    for (size_t i = 1; i < r->shard_ctx.size(); i++) {
+        const int e = smr_sync(r->shard_ctx[i]);
+        if (e < 0 && rc >= 0) rc = shard_gpu(r, r->shard_ctx[i], e, "sync");
     }
     return rc;
 }

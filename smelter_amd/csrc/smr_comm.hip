@@ -4,13 +4,15 @@
 //
 // Two ways to own several GPUs, one gather entry point:
 //   * local  — one process, one smr_ctx per device (what smelter-core's single renderer thread would hold,
-//              smelter-core/src/pipeline/instance.rs:435-503): peer copies, hipMemcpy2DAsync on the owner's stream, the root's
-//              stream waits on an event per sender.  Each peer has its own xGMI link to the root.
+//              smelter-core/src/pipeline/instance.rs:435-503): k_move_rects (smr_move_rects.h) on the owner's stream stores the owner's
+//              tiles into the root's memory, one launch per owner and call; the root's stream waits on an event per sender.  Each peer
+//              has its own xGMI link to the root.
 //   * ranks  — one process per GPU: RCCL point-to-point (ncclSend / ncclRecv in one group) on the ctx stream.  librccl is
 //              opened on first use, so a single-GPU host never needs it.
 // Everything is stream-ordered: a tile is sent after the ingest kernel that wrote it and composed after it arrived; nothing
 // here synchronises the host.
 #include "smr_internal.h"
+#include "smr_move_rects.h"
 
 #include <dlfcn.h>
 #include <mutex>
@@ -74,8 +76,25 @@ struct smr_comm {
     std::vector<smr_ctx *> ctxs;   // local: one per rank; ranks: {own ctx}
     std::vector<hipEvent_t> sent;  // local: one per rank, recorded after its copies
     ncclComm_t nccl = nullptr;
+    bool copies = false;  // SMR_GATHER_COPIES=1 (laboratory builds, A/B: tools/shard_rate.py): one hipMemcpy2DAsync per tile, the transport before k_move_rects
     std::string err;
 };
+
+// One launch of k_move_rects per 16 rectangles on the owner's stream (the owner's device is current).
+static int move_rects(smr_ctx *o, const MoveRect *rects, size_t n) {
+    for (size_t at = 0; at < n; at += SMR_MOVE_MAX_RECTS) {
+        MoveBatch B;
+        memset(&B, 0, sizeof(B));
+        B.n = (u32)(n - at < SMR_MOVE_MAX_RECTS ? n - at : SMR_MOVE_MAX_RECTS);
+        for (u32 i = 0; i < B.n; i++) B.r[i] = rects[at + i];
+        const u32 blocks = mv_plan(B);
+        if (!blocks) continue;
+        o->kernel_launches[SMR_KERNEL_MOVE_RECTS]++;
+        hipLaunchKernelGGL(k_move_rects, dim3(blocks), dim3(SMR_MOVE_BLOCK), 0, o->stream, B);
+        SMR_HIP(o, hipGetLastError());
+    }
+    return SMR_OK;
+}
 
 static int comm_fail(smr_comm *c, smr_ctx *ctx, int code, const std::string &msg) {
     if (c) c->err = msg;
@@ -95,6 +114,9 @@ int smr_comm_create_local(smr_ctx *const *ctxs, uint32_t n, smr_comm **out) {
     c->local = true;
     c->ctxs.assign(ctxs, ctxs + n);
     c->sent.assign(n, nullptr);
+#ifdef SMR_LAB
+    if (const char *e = getenv("SMR_GATHER_COPIES")) c->copies = atoi(e) != 0;
+#endif
     for (uint32_t i = 0; i < n; i++) {
         if (hipSetDevice(ctxs[i]->device) != hipSuccess || hipEventCreateWithFlags(&c->sent[i], hipEventDisableTiming) != hipSuccess) {
             int rc = comm_fail(nullptr, ctxs[i], SMR_ERR_INTERNAL, "smr_comm_create_local: event creation failed");
@@ -191,24 +213,37 @@ int smr_gather_tiles(smr_comm *c, uint32_t root, const uint32_t *owner, const sm
             return comm_fail(c, me, SMR_ERR_INVALID, "smr_gather_tiles: tile " + std::to_string(i) + " differs between owner and root");
     }
     if (c->local) {
-        // owner's stream: wait until the root is done with the destination (its previous compose), copy, signal
-        std::vector<u8> used(c->world, 0);
+        // owner's stream: wait until the root is done with the destination (its previous compose), move, signal
+        for (uint32_t i = 0; i < n; i++)
+            if (owner[i] != root && (src[i]->pitch > 0xffffffffull || dst[i]->pitch > 0xffffffffull))
+                return comm_fail(c, me, SMR_ERR_INVALID, "smr_gather_tiles: tile " + std::to_string(i) + " has a pitch of 4 GiB or more");
         hipEvent_t root_free = c->sent[root];
         SMR_HIP(me, hipSetDevice(me->device));
         SMR_HIP(me, hipEventRecord(root_free, me->stream));
-        for (uint32_t i = 0; i < n; i++) {
-            if (owner[i] == root) continue;
-            smr_ctx *o = c->ctxs[owner[i]];
-            SMR_HIP(o, hipSetDevice(o->device));
-            if (!used[owner[i]]) SMR_HIP(o, hipStreamWaitEvent(o->stream, root_free, 0));
-            used[owner[i]] = 1;
-            SMR_HIP(o, hipMemcpy2DAsync(dst[i]->ptr, dst[i]->pitch, src[i]->ptr, src[i]->pitch, (size_t)src[i]->w * bytes_per_px(src[i]->fmt), src[i]->h,
-                                        hipMemcpyDeviceToDevice, o->stream));
-        }
+        std::vector<MoveRect> rects;
         for (uint32_t r = 0; r < c->world; r++) {
-            if (!used[r]) continue;
+            if (r == root) continue;
+            rects.clear();
+            for (uint32_t i = 0; i < n; i++) {
+                if (owner[i] != r) continue;
+                MoveRect R;
+                R.src = (const u8 *)src[i]->ptr; R.dst = (u8 *)dst[i]->ptr;
+                R.src_pitch = (u32)src[i]->pitch; R.dst_pitch = (u32)dst[i]->pitch;
+                R.row_bytes = src[i]->w * bytes_per_px(src[i]->fmt); R.rows = src[i]->h;
+                rects.push_back(R);
+            }
+            if (rects.empty()) continue;
             smr_ctx *o = c->ctxs[r];
             SMR_HIP(o, hipSetDevice(o->device));
+            SMR_HIP(o, hipStreamWaitEvent(o->stream, root_free, 0));
+            if (SMR_LAB_BUILD && c->copies) {
+                for (const MoveRect &R : rects)
+                    SMR_HIP(o, hipMemcpy2DAsync(R.dst, R.dst_pitch, R.src, R.src_pitch, R.row_bytes, R.rows, hipMemcpyDeviceToDevice, o->stream));
+            } else if (int rc = move_rects(o, rects.data(), rects.size())) {
+                c->err = o->err;
+                (void)hipSetDevice(me->device);
+                return rc;
+            }
             SMR_HIP(o, hipEventRecord(c->sent[r], o->stream));
             SMR_HIP(me, hipSetDevice(me->device));
             SMR_HIP(me, hipStreamWaitEvent(me->stream, c->sent[r], 0));

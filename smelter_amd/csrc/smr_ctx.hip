@@ -310,6 +310,9 @@ int smr_profile_read(smr_ctx *ctx, int stage, float *total_ms, uint32_t *launche
     return SMR_OK;
 }
 
+// the HIP device of a context: for the renderer (host/renderer.cpp, smr_renderer_add_shard), not part of the ABI
+int smr_ctx_device_index(const smr_ctx *ctx) { return ctx ? ctx->device : -1; }
+
 int smr_debug_kernel_launches(const smr_ctx *ctx, uint32_t kernel, uint64_t *count) {
     if (!ctx || !count || kernel >= SMR_KERNEL_COUNT_) return SMR_ERR_INVALID;
     *count = ctx->kernel_launches[kernel];

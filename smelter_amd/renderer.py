@@ -29,8 +29,12 @@ class BorrowedFrame(DeviceFrame):
 
 
 class Renderer:
-    def __init__(self, ctx: Context, stream_fallback_timeout_s: float = 0.5, lanes: Sequence[Context] = (), max_outputs: int = 16):
-        """`lanes`: extra contexts on the same device — consecutive frames rotate through `ctx` and these, so up to
+    def __init__(self, ctx: Context, stream_fallback_timeout_s: float = 0.5, lanes: Sequence[Context] = (), max_outputs: int = 16,
+                 shards: Sequence[Context] = ()):
+        """`shards`: further contexts — usually one per device — that take a share of the inputs (smr_renderer_add_shard): the k-th registered
+        input lives on context k mod (1 + len(shards)) of [ctx] + shards, `input_context(id)` says which; its frames are created / uploaded
+        there.  Outputs are composed on `ctx`.  Does not combine with `lanes`.
+        `lanes`: extra contexts on the same device — consecutive frames rotate through `ctx` and these, so up to
         1 + len(lanes) frames are in flight on the GPU while the scene stays one state (smr_renderer_add_lane).
         `max_outputs`: how many output frames one render call can hand back (the `cap` of smr_renderer_render)."""
         self.ctx, self.lib = ctx, ctx.lib
@@ -44,9 +48,26 @@ class Renderer:
         for c in lanes:
             self._check(self.lib.smr_renderer_add_lane(self._h, c.handle))
             self._ctx_of[c.handle.value] = c
+        for c in shards:
+            self._check(self.lib.smr_renderer_add_shard(self._h, c.handle))
+            self._ctx_of[c.handle.value] = c
+
+    def add_shard(self, ctx: Context):
+        self._check(self.lib.smr_renderer_add_shard(self._h, ctx.handle))
+        self._ctx_of[ctx.handle.value] = ctx
+
+    def add_lane(self, ctx: Context):
+        self._check(self.lib.smr_renderer_add_lane(self._h, ctx.handle))
+        self._ctx_of[ctx.handle.value] = ctx
+
+    def input_context(self, input_id: str) -> Context:
+        """The context the frames of `input_id` must be resident on (smr_renderer_input_ctx)."""
+        h = C.c_void_p()
+        self._check(self.lib.smr_renderer_input_ctx(self._h, input_id.encode(), C.byref(h)))
+        return self._ctx_of[h.value]
 
     def sync(self):
-        """Waits for the frames in flight on every lane."""
+        """Waits for the frames in flight on every lane and shard."""
         self._check(self.lib.smr_renderer_sync(self._h))
 
     def output(self, i: int = 0) -> "BorrowedFrame":
