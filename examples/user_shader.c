@@ -1,0 +1,83 @@
+/* A user shader from C: a fragment function written in HIP C++ is compiled when it is registered (include/smr.h "user shaders") and
+ * drawn by a Shader node.  The shader here is a vignette: source 0 darkened towards the corners, `strength` from the node's shader_param.
+ *   gcc -std=c11 -Iinclude examples/user_shader.c -o user_shader -Lsmelter_amd -l:libsmr_hip.so -Wl,-rpath,$PWD/smelter_amd -lm
+ * Exit codes: 0 ok, 2 no HIP device (the shader was still compiled: that needs none), 1 anything else. */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "smr.h"
+
+static const char *VIGNETTE =
+    "__device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float2 position) {\n"
+    "    const float strength = smr_param<float>(in);\n"
+    "    const float dx = uv.x - 0.5f, dy = uv.y - 0.5f;\n"
+    "    const float k = 1.0f - strength * smr_smoothstep(0.2f, 0.75f, sqrtf(dx * dx + dy * dy));\n"
+    "    const float4 s = smr_sample(in, plane_id, uv.x, uv.y);\n"
+    "    return make_float4(s.x * k, s.y * k, s.z * k, s.w);\n"
+    "}\n";
+
+static const char *SCENE =
+    "{\"type\":\"shader\",\"shader_id\":\"vignette\",\"resolution\":{\"width\":640,\"height\":360},"
+    "\"shader_param\":{\"type\":\"f32\",\"value\":0.8},\"children\":[{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
+
+int main(void) {
+    /* host only: compile, show what the compiler said */
+    smr_shader_program *prog = NULL;
+    int rc = smr_shader_program_create(VIGNETTE, &prog);
+    if (rc != SMR_OK) {
+        fprintf(stderr, "the shader did not compile (%d):\n%s\n", rc, prog ? smr_shader_program_log(prog) : "");
+        smr_shader_program_destroy(prog);
+        return 1;
+    }
+    const void *code = NULL;
+    size_t code_size = 0;
+    smr_shader_program_code(prog, &code, &code_size);
+    printf("vignette: %zu bytes of gfx950 code\n", code_size);
+
+    smr_ctx *ctx = NULL;
+    if (smr_ctx_create(0, SMR_MODE_GPU_OPTIMIZED, SMR_DEFAULT_MAX_LAYOUTS, NULL, &ctx) != SMR_OK) {
+        fprintf(stderr, "no HIP device\n");
+        smr_shader_program_destroy(prog);
+        return 2;
+    }
+    smr_renderer *r = NULL;
+    int status = 1;
+    smr_frame cam;
+    memset(&cam, 0, sizeof(cam));
+    if (smr_renderer_create(ctx, -1, &r) != 0) goto out;
+    if (smr_renderer_register_input(r, "cam") != 0 || smr_renderer_register_shader_program(r, "vignette", prog) != 0 ||
+        smr_renderer_update_scene(r, "out", 640, 360, SMR_FRAME_RGBA, SCENE) != 0) {
+        fprintf(stderr, "%s\n", smr_renderer_last_error(r));
+        goto out;
+    }
+    if (smr_frame_create(ctx, SMR_FRAME_RGBA, 320, 180, &cam) != SMR_OK) goto out;
+    {
+        uint8_t *px = malloc(320 * 180 * 4);
+        const void *planes[3] = {px, NULL, NULL};
+        memset(px, 200, 320 * 180 * 4);
+        smr_frame_upload(ctx, &cam, planes);
+        free(px);
+        smr_input_frame in = {"cam", &cam, 0};
+        smr_output_frame out[1];
+        uint32_t n = 0;
+        if (smr_renderer_render(r, 0, &in, 1, out, 1, &n) != 0 || n != 1) {
+            fprintf(stderr, "%s\n", smr_renderer_last_error(r));
+            goto out;
+        }
+        uint8_t *got = malloc(640 * 360 * 4);
+        void *dst[3] = {got, NULL, NULL};
+        smr_frame_download(out[0].ctx, out[0].frame, dst);
+        uint64_t launches = 0;
+        smr_shader_program_launches(prog, &launches);
+        printf("centre %u, corner %u, launches %llu\n", got[(180 * 640 + 320) * 4], got[0], (unsigned long long)launches);
+        status = got[(180 * 640 + 320) * 4] > got[0] && launches == 1 ? 0 : 1;
+        free(got);
+    }
+out:
+    if (r) smr_renderer_destroy(r);
+    smr_frame_destroy(ctx, &cam);
+    smr_ctx_destroy(ctx);
+    smr_shader_program_destroy(prog); /* after the renderer it was registered in */
+    return status;
+}

@@ -407,9 +407,9 @@ SMR_API int smr_fontbook_measure(void *book, const smr_text_params *params, floa
 SMR_API int smr_fontbook_rasterise(smr_fontbook *book, const smr_text_params *params, uint32_t width, uint32_t height, const float color[4],
                                    smr_text_run *out);
 
-/* ---- a13 stand-in: built-in "shader" kernels (user WGSL is out of scope) ------------ */
-/* Built-in kernels for ShaderNode::render (transformations/shader/node.rs:71-89, shader/pipeline.rs:81-141).  Arbitrary user
- * WGSL needs a compiler this library does not carry; what ships are the shaders the reference keeps in its own tree,
+/* ---- a13: the Shader node — built-in kernels, and user shaders written in HIP C++ ---- */
+/* Built-in kernels for ShaderNode::render (transformations/shader/node.rs:71-89, shader/pipeline.rs:81-141).  User WGSL needs a
+ * compiler this library does not carry (user shaders in HIP C++: below); built in are the shaders the reference keeps in its own tree,
  * restated as HIP kernels with the node's semantics: the target is cleared to transparent, one full-target plane is drawn per
  * source texture (plane_id 0..n-1; a single plane with plane_id -1 when there are none), premultiplied-alpha OVER, each plane
  * stored to the RGBA8 target before the next is blended.  BaseShaderParameters {plane_id, time, output_resolution,
@@ -437,6 +437,52 @@ typedef struct smr_circle_layout { uint32_t left_px, top_px, width_px, height_px
 typedef struct smr_gaussian_blur_params { float sigma; } smr_gaussian_blur_params;
 SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, size_t params_size,
                                const smr_surface *const *src, uint32_t n_src, smr_surface *dst, float time_s);
+
+/* User shaders.  A Shader component runs the caller's own fragment function; here it is written in HIP C++ and compiled to a gfx950
+ * code object by the ROCm runtime compiler (libhiprtc.so, loaded on first use) when the shader is registered.  A shader is ONE
+ * translation unit that includes nothing and defines
+ *     __device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float2 position);
+ *     // optional, announced with `#define SMR_HAS_VERTEX` at the top of the source:
+ *     __device__ smr_plane smr_vertex(const smr_shader_in &in, int plane_id);
+ * The node's semantics are those of the built-in kernels (the same kernel with the user's functions in place of the built-in switch):
+ * the target is cleared to transparent, one plane per source is drawn in order (plane_id 0 .. texture_count - 1; one plane with
+ * plane_id -1 when the node has no children), every plane blended premultiplied-alpha OVER and stored to the RGBA8 target before the
+ * next.  smr_fragment gets the fragment's tex_coords `uv` within the plane and its pixel-centre `position` (@builtin(position).xy) and
+ * returns premultiplied RGBA in the target's blending space (linear light in SMR_MODE_GPU_OPTIMIZED, unorm values in
+ * SMR_MODE_CPU_OPTIMIZED).  smr_vertex returns smr_plane {sx, sy, cx, cy}: the unit quad's corners go to clip-space position * (sx, sy) +
+ * (cx, cy).  The vertex stage is an axis-aligned scale + translate and nothing else: rotated, sheared or otherwise deformed planes are
+ * NOT expressible (a plane with sx <= 0 or sy <= 0 covers nothing).  Without smr_vertex every plane covers the target.
+ * What a shader may use (the library puts it in front of the source):
+ *     in.time (seconds, float)   in.output_resolution (uint2)   in.texture_count (int)          BaseShaderParameters (base_params.rs:7-12)
+ *     float4 smr_sample(in, i, u, v)        source i through the linear clamp-to-edge sampler, decoded to the blending space;
+ *                                           (0, 0, 0, 0) when i is out of range or the source is absent
+ *     T smr_param<T>(in)   const unsigned char *smr_param_bytes(in)   unsigned smr_param_size(in)
+ *                                           the @group(1) uniform: the shader_param's values in order, little endian, no padding
+ *                                           (ShaderParam::to_bytes); bytes behind smr_param_size read 0
+ *     float smr_smoothstep(e0, e1, x)       WGSL smoothstep;  make_float2 / make_float4 and the HIP device math library (sqrtf, sinf, ...)
+ * A shader never holds a pointer into a surface: every access goes through smr_sample, which clamps — it cannot read or write outside
+ * its sources and target.  It is compiled with the library's own options (--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off):
+ * every multiply and add is rounded on its own, as in the built-in kernels.  Compiling takes of the order of a second (DESIGN.md
+ * section 3e): register shaders off the render thread. */
+typedef struct smr_shader_program smr_shader_program;
+#define SMR_SHADER_MAX_PARAM_BYTES 2048
+/* Host only: needs no device and no context.  A source that does not compile returns SMR_ERR_INVALID and STILL hands out a program
+ * object: smr_shader_program_log has the compiler's message ("shader:LINE:COLUMN: error: ..." — lines of the caller's source); such a
+ * program cannot be registered or launched and is destroyed like any other.  No runtime compiler on the machine: SMR_ERR_INTERNAL, the
+ * log names libhiprtc.so. */
+SMR_API int smr_shader_program_create(const char *hip_source, smr_shader_program **out);
+SMR_API const char *smr_shader_program_log(const smr_shader_program *p); /* errors and warnings, "" if none */
+SMR_API int smr_shader_program_code(const smr_shader_program *p, const void **code, size_t *size); /* the gfx950 code object (tools/kernel_resources.py reads it) */
+/* Launches of this program so far, over all contexts (which path rendered a Shader node is observable without a kernel counter slot) */
+SMR_API int smr_shader_program_launches(const smr_shader_program *p, uint64_t *count);
+/* Unloads the program's modules (after waiting for the devices that ran them).  A program must outlive its registrations. */
+SMR_API void smr_shader_program_destroy(smr_shader_program *p);
+/* Twin of smr_builtin_shader.  The code object is loaded once per device at the first launch there (shared by every context on the
+ * device; unloaded with the program or the last of those contexts, whichever goes first); sources, target, time and the parameter
+ * bytes travel by value in the kernel arguments — nothing is uploaded, nothing blocks, `params` may be freed on return.
+ * SMR_ERR_INVALID: more than SMR_SHADER_MAX_PARAM_BYTES, more than SMR_SHADER_MAX_SOURCES, a target or source that is not RGBA8. */
+SMR_API int smr_user_shader(smr_ctx *ctx, const smr_shader_program *p, const void *params, size_t params_size,
+                            const smr_surface *const *src, uint32_t n_src, smr_surface *dst, float time_s);
 
 /* ---- a5/a6: host scene engine (no GPU work) ------------------------------------------
  * Scene JSON (the smelter-api component schema, smelter-api/src/video/component.rs) -> stateful
@@ -507,7 +553,8 @@ SMR_API int smr_parse_color(const char *text, uint8_t rgba[4]);
  *   Renderer::new              -> smr_renderer_create (stream_fallback_timeout: state.rs:43-52, render_loop.rs:29)
  *   register_input / unregister_input / unregister_output (state.rs:102-121)
  *   register_renderer(Image)   -> smr_renderer_register_image (bitmap pixels; decoding is the caller's)
- *   register_renderer(Shader)  -> smr_renderer_register_shader (a built-in kernel id; user WGSL is out of scope)
+ *   register_renderer(Shader)  -> smr_renderer_register_shader (a built-in kernel id), smr_renderer_register_shader_source /
+ *                                 _program (a user shader written in HIP C++; WGSL text is out of scope)
  *   update_scene               -> smr_renderer_update_scene(output_id, resolution, OutputFrameFormat, scene JSON) (state.rs:177-189)
  *   render(FrameSet<InputId>)  -> smr_renderer_render: populate_inputs (stale frames dropped), depth-first walk of every output's
  *                                 render graph (input refs, images, text, shader and nested layout nodes), read_outputs fused
@@ -535,6 +582,14 @@ SMR_API int smr_renderer_register_input(smr_renderer *r, const char *input_id);
 SMR_API int smr_renderer_unregister_input(smr_renderer *r, const char *input_id);
 SMR_API int smr_renderer_register_image(smr_renderer *r, const char *image_id, const uint8_t *rgba_straight, uint32_t width, uint32_t height);
 SMR_API int smr_renderer_register_shader(smr_renderer *r, const char *shader_id, uint32_t builtin_id);
+/* A user shader ("user shaders" above) under `shader_id`; registering an id again replaces what it named (built-in or not).
+ * _source compiles (blocking, host only) and the renderer owns the program; a source that does not compile fails with the status of
+ * smr_shader_program_create, the compiler's log in smr_renderer_last_error (RegisterRendererError), and the registry unchanged.
+ * _program registers a compiled program the caller keeps: it must outlive the registration (until the id is re-registered or the
+ * renderer destroyed).  Works with lanes and shards (Shader nodes render on the renderer's own context) and in both rendering modes;
+ * a user shader's output is never treated as opaque. */
+SMR_API int smr_renderer_register_shader_source(smr_renderer *r, const char *shader_id, const char *hip_source);
+SMR_API int smr_renderer_register_shader_program(smr_renderer *r, const char *shader_id, const smr_shader_program *p);
 /* An update is refused as a whole — the previous scene stays active — for everything the scene definition can get wrong: validation errors,
  * unknown shader ids, and (with a font book) Text nodes no run can be made of (empty font book, text that is not UTF-8, absurd sizes).  One
  * failure is reported AFTER the new scene is in place: a device allocation that fails while the output's frames or a Text node's surface are
@@ -585,7 +640,8 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      SMR_CONVERT_GENERAL / SMR_DISABLE_FUSED / SMR_COMPOSE_SELECT environment knobs are smr_ctx_set_option options in a product build
  *      (the environment is read by laboratory builds only).
  *      Added since, without a new version (additions only: nothing a version-2 host calls changed): SMR_KERNEL_MOVE_RECTS (counter slot 8),
- *      smr_renderer_add_shard, smr_renderer_input_ctx.
+ *      smr_renderer_add_shard, smr_renderer_input_ctx; user shaders (smr_shader_program_*, smr_user_shader,
+ *      smr_renderer_register_shader_source / _program).
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

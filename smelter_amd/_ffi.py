@@ -22,6 +22,7 @@ SOURCE_NONE, SOURCE_SURFACE, SOURCE_FRAME, SOURCE_OPAQUE_SURFACE = 0, 1, 2, 3
 SHADER_GAUSSIAN_BLUR, SHADER_GRADIENT, SHADER_RED_BORDER, SHADER_CIRCLE_LAYOUT = 0, 1, 2, 3
 SHADER_FADE_TO_BALL, SHADER_LAYOUT_PLANES, SHADER_COLOR_BY_TEXTURE_COUNT, SHADER_SILLY = 4, 5, 6, 7
 SHADER_MAX_SOURCES = 16
+SHADER_MAX_PARAM_BYTES = 2048
 
 # every symbol include/smr.h declares (checked by tests/test_abi.py without a GPU)
 EXPORTS = [
@@ -47,6 +48,8 @@ EXPORTS = [
     "smr_comm_last_error", "smr_gather_tiles",
     "smr_fontbook_create", "smr_fontbook_destroy", "smr_fontbook_last_error", "smr_fontbook_add_file", "smr_fontbook_add_memory",
     "smr_fontbook_add_dir", "smr_fontbook_count", "smr_fontbook_measure", "smr_fontbook_rasterise", "smr_renderer_set_fontbook",
+    "smr_shader_program_create", "smr_shader_program_log", "smr_shader_program_code", "smr_shader_program_launches",
+    "smr_shader_program_destroy", "smr_user_shader", "smr_renderer_register_shader_source", "smr_renderer_register_shader_program",
     "smr_abi_version", "smr_build_flags", "smr_sizeof_layout",
 ]
 NO_RESOLUTION = 0xFFFFFFFF
@@ -242,6 +245,14 @@ def load():
         "smr_fontbook_measure": ([P, C.POINTER(TextParams), C.POINTER(F), C.POINTER(U)], I),
         "smr_fontbook_rasterise": ([P, C.POINTER(TextParams), U, U, C.POINTER(F), C.POINTER(TextRun)], I),
         "smr_renderer_set_fontbook": ([P, P], I),
+        "smr_shader_program_create": ([C.c_char_p, PP], I),
+        "smr_shader_program_log": ([P], C.c_char_p),
+        "smr_shader_program_code": ([P, PP, C.POINTER(C.c_size_t)], I),
+        "smr_shader_program_launches": ([P, C.POINTER(C.c_uint64)], I),
+        "smr_shader_program_destroy": ([P], None),
+        "smr_user_shader": ([P, P, P, C.c_size_t, PP, U, P, F], I),
+        "smr_renderer_register_shader_source": ([P, C.c_char_p, C.c_char_p], I),
+        "smr_renderer_register_shader_program": ([P, C.c_char_p, P], I),
         "smr_abi_version": ([], U),
         "smr_build_flags": ([], U),
         "smr_sizeof_layout": ([], U),

@@ -18,6 +18,7 @@
 #include <set>
 
 #include "scene.h"
+#include "shader_program.h"
 
 using namespace smr_host;
 
@@ -121,7 +122,11 @@ struct smr_renderer {
     int64_t timeout_ns = 500000000;  // stream_fallback_timeout
     std::set<std::string> inputs;
     std::map<std::string, ImageRes> images;
-    std::map<std::string, uint32_t> shaders;  // shader_id -> smr_builtin_shader_id
+    struct ShaderReg {                // a built-in kernel id, or (hook.launch set) a user shader program: shader_program.h
+        uint32_t builtin = 0;
+        smr_shader_hook hook;
+    };
+    std::map<std::string, ShaderReg> shaders;
     smr_text_measure_fn measure = nullptr;    // the caller's text shaper (fitted Text nodes)
     void *measure_user = nullptr;
     smr_fontbook *fontbook = nullptr;         // TextRendererCtx: with a book, Text nodes are measured and drawn here (not owned)
@@ -439,7 +444,17 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
         // the @group(1) uniform: ShaderParam::to_bytes (shader/node.rs:95-112), the values in order, little endian, no padding
         std::vector<uint8_t> params;
         flatten_shader_param(c.shader_param, params);
-        if (it->second == SMR_SHADER_GAUSSIAN_BLUR) {
+        const smr_renderer::ShaderReg &reg = it->second;
+        if (reg.hook.launch) {
+            // a user shader: the same sources, parameter bytes and pts; its output is never known to be opaque
+            rc = gpu(r, reg.hook.launch(reg.hook.user, r->ctx, params.data(), params.size(), srcs.data(), (uint32_t)srcs.size(), o.l->node_surface[idx],
+                                        (float)((double)fs.pts_ns / 1e9)),
+                     "shader node");
+            if (rc < 0) return rc;
+            out.kind = SMR_SOURCE_SURFACE; out.surface = o.l->node_surface[idx]; out.w = w; out.h = h;
+            return 0;
+        }
+        if (reg.builtin == SMR_SHADER_GAUSSIAN_BLUR) {
             if (srcs.empty()) return 0;  // nothing to sample: the node stays empty
             // the blur kernel maps texel to texel: a source of another size is first brought to the node's resolution
             const smr_surface *src0 = srcs[0];
@@ -460,7 +475,7 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
             }
             if (params.size() < sizeof(smr_gaussian_blur_params)) params.assign(sizeof(smr_gaussian_blur_params), 0);
         }
-        rc = gpu(r, smr_builtin_shader(r->ctx, it->second, params.data(), params.size(), srcs.data(), (uint32_t)srcs.size(), o.l->node_surface[idx],
+        rc = gpu(r, smr_builtin_shader(r->ctx, reg.builtin, params.data(), params.size(), srcs.data(), (uint32_t)srcs.size(), o.l->node_surface[idx],
                                        (float)((double)fs.pts_ns / 1e9)),
                  "shader node");
         if (rc < 0) return rc;
@@ -566,6 +581,20 @@ int render_output(smr_renderer *r, Output &o, const FrameSetView &fs, const smr_
 
 }  // namespace
 
+// Renderer::register_renderer(Shader) for everything that is not a built-in id (shader_program.cpp); re-registering an id replaces it
+int smr_renderer_register_shader_hook(smr_renderer *r, const char *shader_id, const smr_shader_hook &hook) {
+    if (!r || !shader_id) return fail(r, -1, "smr_renderer_register_shader: null argument");
+    smr_renderer::ShaderReg &reg = r->shaders[shader_id];
+    if (reg.hook.release) {
+        sync_lanes(r);  // frames in flight may still run the program that goes
+        reg.hook.release(reg.hook.user);
+    }
+    reg.builtin = 0;
+    reg.hook = hook;
+    return 0;
+}
+int smr_renderer_fail(smr_renderer *r, int code, const std::string &msg) { return fail(r, code, msg); }
+
 extern "C" {
 
 SMR_API int smr_renderer_create(smr_ctx *ctx, int64_t stream_fallback_timeout_ns, smr_renderer **out) {
@@ -574,7 +603,7 @@ SMR_API int smr_renderer_create(smr_ctx *ctx, int64_t stream_fallback_timeout_ns
     r->ctx = ctx;
     r->lane_ctx.push_back(ctx);
     if (stream_fallback_timeout_ns >= 0) r->timeout_ns = stream_fallback_timeout_ns;
-    r->shaders["gaussian_blur"] = SMR_SHADER_GAUSSIAN_BLUR;
+    r->shaders["gaussian_blur"].builtin = SMR_SHADER_GAUSSIAN_BLUR;
     *out = r;
     return 0;
 }
@@ -586,6 +615,8 @@ SMR_API void smr_renderer_destroy(smr_renderer *r) {
     for (auto &kv : r->images)
         if (kv.second.surface) smr_surface_destroy(r->ctx, kv.second.surface);
     if (r->comm) smr_comm_destroy(r->comm);
+    for (auto &kv : r->shaders)
+        if (kv.second.hook.release) kv.second.hook.release(kv.second.hook.user);
     delete r;
 }
 
@@ -651,7 +682,9 @@ SMR_API int smr_renderer_set_fontbook(smr_renderer *r, smr_fontbook *book) {
 SMR_API int smr_renderer_register_shader(smr_renderer *r, const char *shader_id, uint32_t builtin_id) {
     if (!r || !shader_id) return fail(r, -1, "smr_renderer_register_shader: null argument");
     if (builtin_id > SMR_SHADER_SILLY) return fail(r, -1, "smr_renderer_register_shader: unknown built-in shader (user WGSL is not supported)");
-    r->shaders[shader_id] = builtin_id;
+    smr_shader_hook none;
+    smr_renderer_register_shader_hook(r, shader_id, none);
+    r->shaders[shader_id].builtin = builtin_id;
     return 0;
 }
 

@@ -195,6 +195,7 @@ void smr_ctx_destroy(smr_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     drain_profile(ctx);
+    smr_user_shader_ctx_gone(ctx);  // user shader modules this context was the last user of (smr_user_shader.hip)
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
     for (auto &s : ctx->scratch)
         if (s.ptr) (void)hipFree(s.ptr);

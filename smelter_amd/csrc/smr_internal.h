@@ -30,13 +30,10 @@ constexpr bool SMR_LAB_BUILD = false;
 #endif
 
 
-typedef uint8_t u8;
-typedef uint16_t u16;
-typedef uint32_t u32;
+#include "smr_shader_dev.h"  // u8 / u16 / u32, SurfView and the texel helpers the built-in and the user shaders share
 
-// sRGB table block (layout documented at srgb_encode8 below)
+// sRGB table block (layout documented at srgb_encode8, smr_shader_dev.h, which also defines SMR_ENC_OFFSET_FROM_THR)
 #define SMR_TABLE_FLOATS 932
-#define SMR_ENC_OFFSET_FROM_THR 260
 #define SMR_ENC_ENTRIES 1664
 // lut16 block (device: ctx->d_lut16): [0,256) the decode table as (f16 hi | f16 lo << 16) | [256, 256 + SMR_ENC_ENTRIES) the encode table of the
 // matrix-core resampler: per estimate bucket (code of its lowest x) << 16 | 0xffff - (offset of the one threshold inside it - 1; 0xffff = none)
@@ -63,13 +60,6 @@ struct smr_surface {
     bool owned = false;
     size_t capacity = 0;  // bytes behind ptr when owned (cached scratch surfaces are re-described in place while they fit)
 
-};
-
-// Device-side view of a surface.
-struct SurfView {
-    u8 *ptr;
-    u32 pitch;
-    int w, h;
 };
 
 // ---- device memory through GLOBAL instructions.  A pointer the compiler cannot trace back to a kernel argument — rebuilt from integers
@@ -226,6 +216,7 @@ struct smr_ctx {
 // ctx-owned surface for `slot`, (re)allocated when the requested geometry changes; nullptr on error
 smr_surface *smr_cached_surface(smr_ctx *ctx, size_t slot, u32 w, u32 h, u32 fmt);
 
+void smr_user_shader_ctx_gone(smr_ctx *ctx);  // smr_user_shader.hip: called by smr_ctx_destroy
 int smr_fail(smr_ctx *ctx, int code, const char *fmt, ...);
 int smr_check_hip(smr_ctx *ctx, hipError_t e, const char *what);
 void *smr_scratch(smr_ctx *ctx, int slot, size_t bytes);  // nullptr on OOM (error set)
@@ -299,38 +290,7 @@ static inline u32 bytes_per_px(u32 fmt) {
 // ------------------------------------------------------------------ device helpers
 #ifdef __HIPCC__
 
-// Pixel interpretation used by filter kernels (same numbering as the oracle).
-enum { PXI_RGBA8_SRGB = 0, PXI_RGBA8_UNORM = 1, PXI_RGBA16F = 2 };
-
-__device__ __forceinline__ float clampf(float x, float lo, float hi) {
-    // WGSL clamp: min(max(x, lo), hi); NaN -> lo
-    if (!(x > lo)) return lo;
-    if (x > hi) return hi;
-    return x;
-}
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-__device__ __forceinline__ u32 unorm8(float x) {
-    x = clampf(x, 0.0f, 1.0f);
-    return (u32)(int)(x * 255.0f + 0.5f);
-}
-
-// sRGB encode as the monotone step function u8 = #{i : thr[i] <= x}.  Table block layout
-// (SMR_TABLE_FLOATS floats, built in smr_ctx_create, copied to LDS by the hot kernels):
-//   [0,256)    decode LUT            [256,513)  thr[0..256] (thr[0] = -inf, thr[256] = +inf)
-//   [516,932)  enc: 1664 bytes, enc[((bits(x) - bits(2^-13)) >> 16)] = code of the bucket's lowest x
-// A bucket (7 mantissa bits) straddles at most two thresholds (checked when the table is built),
-// so the estimate needs at most two upward fix-up steps: exact, branch-free, no transcendental.
-__device__ __forceinline__ u32 srgb_encode8(float x, const float *__restrict__ thr) {
-    // branch-free (independent encodes overlap their table latencies): the estimate index is taken from x clamped
-    // into [2^-13, 1); below 2^-13 (< thr[1]; also NaN, negatives) the bucket code is 0 and no threshold is reached,
-    // at and above 1 the last bucket's code steps up to 255 through thr[255] (thr[256] = +inf ends the count).
-    const u8 *enc = (const u8 *)(thr + SMR_ENC_OFFSET_FROM_THR);
-    const float xc = fminf(fmaxf(x, 1.220703125e-4f), 0.99999994f);
-    u32 c = enc[(__float_as_uint(xc) - 0x39000000u) >> 16];
-    c += thr[c + 1] <= x ? 1u : 0u;
-    return c;
-}
+// (PXI_*, clampf, clampi, unorm8, srgb_encode8, subtexel, load_texel, store_texel, sample_rgba_bilinear: smr_shader_dev.h)
 
 // a / b, correctly rounded, from rb = RN(1/b): q0 = RN(a*rb); r = a - q0*b (exact, FMA); q = RN(q0 + r*rb)
 // (Markstein; holds for normal operands unless b's significand is all ones).
@@ -338,48 +298,6 @@ __device__ __forceinline__ float div_cr(float a, float b, float rb) {
     float q0 = a * rb;
     float r = __builtin_fmaf(-q0, b, a);
     return __builtin_fmaf(r, rb, q0);
-}
-
-__device__ __forceinline__ float subtexel(float f) { return floorf(f * 256.0f + 0.5f) / 256.0f; }
-
-__device__ __forceinline__ float4 load_texel(const SurfView &s, int pxi, int x, int y, const float *__restrict__ dec) {
-    float4 o;
-    if (pxi == PXI_RGBA16F) {
-        const uint2 raw = *(const uint2 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 8);
-        __half2 lo = *(const __half2 *)&raw.x, hi = *(const __half2 *)&raw.y;
-        float2 a = __half22float2(lo), b = __half22float2(hi);
-        o = make_float4(a.x, a.y, b.x, b.y);
-    } else {
-        const u32 raw = *(const u32 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 4);
-        u32 r = raw & 0xff, g = (raw >> 8) & 0xff, b = (raw >> 16) & 0xff, a = raw >> 24;
-        if (pxi == PXI_RGBA8_SRGB) {
-            o.x = dec[r]; o.y = dec[g]; o.z = dec[b];
-        } else {
-            o.x = (float)r / 255.0f; o.y = (float)g / 255.0f; o.z = (float)b / 255.0f;
-        }
-        o.w = (float)a / 255.0f;
-    }
-    return o;
-}
-
-__device__ __forceinline__ void store_texel(const SurfView &s, int pxi, int x, int y, float4 v,
-                                            const float *__restrict__ thr) {
-    if (pxi == PXI_RGBA16F) {
-        __half2 lo = __floats2half2_rn(v.x, v.y), hi = __floats2half2_rn(v.z, v.w);
-        uint2 raw;
-        raw.x = *(const u32 *)&lo;
-        raw.y = *(const u32 *)&hi;
-        *(uint2 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 8) = raw;
-    } else {
-        u32 r, g, b;
-        if (pxi == PXI_RGBA8_SRGB) {
-            r = srgb_encode8(v.x, thr); g = srgb_encode8(v.y, thr); b = srgb_encode8(v.z, thr);
-        } else {
-            r = unorm8(v.x); g = unorm8(v.y); b = unorm8(v.z);
-        }
-        u32 a = unorm8(v.w);
-        *(u32 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 4) = r | (g << 8) | (b << 16) | (a << 24);
-    }
 }
 
 // textureSample of one channel of an 8-bit plane (comps interleaved channels), bilinear,
@@ -399,25 +317,6 @@ __device__ __forceinline__ float sample_plane_bilinear(const SurfView &p, int co
     float top = a * (1.0f - fx) + b * fx;
     float bot = cc * (1.0f - fx) + d * fx;
     return top * (1.0f - fy) + bot * fy;
-}
-
-// textureSample of an RGBA8 (or RGBA16F) surface, bilinear + clamp, texels decoded per `pxi`.
-__device__ __forceinline__ float4 sample_rgba_bilinear(const SurfView &s, int pxi, float u, float v,
-                                                       const float *__restrict__ dec) {
-    float sx = u * (float)s.w - 0.5f, sy = v * (float)s.h - 0.5f;
-    float fx0 = floorf(sx), fy0 = floorf(sy);
-    float fx = subtexel(sx - fx0), fy = subtexel(sy - fy0);
-    int x0 = clampi((int)fx0, 0, s.w - 1), x1 = clampi((int)fx0 + 1, 0, s.w - 1);
-    int y0 = clampi((int)fy0, 0, s.h - 1), y1 = clampi((int)fy0 + 1, 0, s.h - 1);
-    float4 a = load_texel(s, pxi, x0, y0, dec), b = load_texel(s, pxi, x1, y0, dec);
-    float4 c = load_texel(s, pxi, x0, y1, dec), d = load_texel(s, pxi, x1, y1, dec);
-    float4 o;
-    float gx = 1.0f - fx, gy = 1.0f - fy;
-    o.x = (a.x * gx + b.x * fx) * gy + (c.x * gx + d.x * fx) * fy;
-    o.y = (a.y * gx + b.y * fx) * gy + (c.y * gx + d.y * fx) * fy;
-    o.z = (a.z * gx + b.z * fx) * gy + (c.z * gx + d.z * fx) * fy;
-    o.w = (a.w * gx + b.w * fx) * gy + (c.w * gx + d.w * fx) * fy;
-    return o;
 }
 
 #endif  // __HIPCC__

@@ -1,10 +1,10 @@
-// smr_misc.hip — text-node glyph blit and the built-in "shader" kernels.
+// smr_misc.hip — text-node glyph blit and the built-in shader kernels.
 //
 // Replaces the per-scene-update raster side of TextRendererNode::render
 // (smelter-render/src/transformations/text_renderer.rs:72-167: Clear(background), then the
-// glyph quads alpha-blended from the coverage atlas) and stands in for ShaderNode::render
-// (transformations/shader/node.rs:71-89) with a library of built-in kernels — arbitrary
-// user WGSL is out of scope (no naga->HIP compiler).
+// glyph quads alpha-blended from the coverage atlas) and ShaderNode::render
+// (transformations/shader/node.rs:71-89) for the library's built-in kernels.  A user's own
+// shader, written in HIP C++, goes through smr_user_shader.hip (WGSL text: no naga->HIP compiler).
 #include "smr_internal.h"
 
 #include <cmath>
@@ -191,7 +191,7 @@ int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, size_t par
     case SMR_SHADER_SILLY:
         return smr_launch_plane_shader(ctx, id, params, params_size, src, n_src, dst, time_s);  // smr_shaders.hip
     default:
-        // RegisterRendererError for unknown shaders; arbitrary WGSL is not supported by this build
+        // RegisterRendererError for unknown shaders (user shaders: smr_user_shader)
         return smr_fail(ctx, SMR_ERR_INVALID, "smr_builtin_shader: unknown built-in shader id %u", id);
     }
 }

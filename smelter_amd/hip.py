@@ -475,3 +475,55 @@ class Context:
         self._check(self.lib.smr_builtin_shader(self.handle, int(shader_id), C.cast(buf, C.c_void_p), len(params), ptrs, len(sources),
                                                 dst.handle, float(time_s)))
         return dst
+
+    def user_shader(self, program: "ShaderProgram", sources, dst: Surface, params: bytes = b"", time_s: float = 0.0) -> Surface:
+        """One ShaderNode render with a user shader (include/smr.h "user shaders"): the twin of `builtin_shader`."""
+        ptrs = (C.c_void_p * max(1, len(sources)))(*[s.handle for s in sources])
+        buf = C.create_string_buffer(bytes(params), max(1, len(params)))
+        self._check(self.lib.smr_user_shader(self.handle, program.handle, C.cast(buf, C.c_void_p), len(params), ptrs, len(sources),
+                                             dst.handle, float(time_s)))
+        return dst
+
+
+class ShaderCompileError(SmrError):
+    """smr_shader_program_create refused the source; `.log` is the compiler's output (lines of the caller's source: "shader:LINE:COL")."""
+
+    def __init__(self, code: int, log: str):
+        super().__init__(code, log)
+        self.log = log
+
+
+class ShaderProgram:
+    """A user shader written in HIP C++, compiled to a gfx950 code object (smr_shader_program_create): needs no device and no context."""
+
+    def __init__(self, source: str):
+        self.lib = _ffi.load()
+        h = C.c_void_p()
+        rc = self.lib.smr_shader_program_create(source.encode(), C.byref(h))
+        self.handle = h if h.value else None
+        if rc != 0:
+            log = self.log if self.handle else "smr_shader_program_create failed"
+            self.close()
+            raise ShaderCompileError(rc, log)
+
+    @property
+    def log(self) -> str:
+        return self.lib.smr_shader_program_log(self.handle).decode(errors="replace")
+
+    @property
+    def code(self) -> bytes:
+        p, n = C.c_void_p(), C.c_size_t()
+        if self.lib.smr_shader_program_code(self.handle, C.byref(p), C.byref(n)) != 0:
+            raise SmrError(_ffi.SMR_ERR_INVALID, "smr_shader_program_code: not a compiled program")
+        return C.string_at(p, n.value)
+
+    @property
+    def launches(self) -> int:
+        n = C.c_uint64()
+        self.lib.smr_shader_program_launches(self.handle, C.byref(n))
+        return n.value
+
+    def close(self):
+        if self.handle:
+            self.lib.smr_shader_program_destroy(self.handle)
+            self.handle = None

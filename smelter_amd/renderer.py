@@ -109,6 +109,16 @@ class Renderer:
     def register_shader(self, shader_id: str, builtin_id: int = _ffi.SHADER_GAUSSIAN_BLUR):
         self._check(self.lib.smr_renderer_register_shader(self._h, shader_id.encode(), builtin_id))
 
+    def register_shader_source(self, shader_id: str, source: str):
+        """A user shader written in HIP C++ (include/smr.h "user shaders"), compiled here; a compile error raises SceneError with the log."""
+        self._check(self.lib.smr_renderer_register_shader_source(self._h, shader_id.encode(), source.encode()))
+
+    def register_shader_program(self, shader_id: str, program):
+        """A compiled smelter_amd.hip.ShaderProgram the caller keeps: it must outlive the registration."""
+        self._programs = getattr(self, "_programs", {})
+        self._programs[shader_id] = program  # keep it alive: the renderer does not own it
+        self._check(self.lib.smr_renderer_register_shader_program(self._h, shader_id.encode(), program.handle))
+
     # -- scenes (state.rs:177-189)
     def update_scene(self, output_id: str, width: int, height: int, scene: Union[str, dict], output_format: int = FRAME_PLANAR_YUV420) -> List[Node]:
         text = scene if isinstance(scene, str) else json.dumps(scene)

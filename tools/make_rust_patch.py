@@ -139,6 +139,11 @@ pub struct smr_comm {
 pub struct smr_fontbook {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct smr_shader_program {
+    _p: [u8; 0],
+}
+pub const SMR_SHADER_MAX_PARAM_BYTES: usize = 2048;
 
 @@ENUMS@@
 pub const SMR_MAX_MASKS: usize = 20; // MAX_MASKS_COUNT (transformations/layout/params.rs:15)
