@@ -1,5 +1,7 @@
 /* A user shader from C: a fragment function written in HIP C++ is compiled when it is registered (include/smr.h "user shaders") and
- * drawn by a Shader node.  The shader here is a vignette: source 0 darkened towards the corners, `strength` from the node's shader_param.
+ * drawn by a Shader node.  The first shader here is a vignette: source 0 darkened towards the corners, `strength` from the node's
+ * shader_param.  The second has an affine vertex stage: its last source turns by in.time radians about the target's centre, its aspect
+ * ratio kept (smr_dimensions); outside that plane the target shows eight bands whose colours are the texels of a palette strip (smr_load).
  *   gcc -std=c11 -Iinclude examples/user_shader.c -o user_shader -Lsmelter_amd -l:libsmr_hip.so -Wl,-rpath,$PWD/smelter_amd -lm
  * Exit codes: 0 ok, 2 no HIP device (the shader was still compiled: that needs none), 1 anything else. */
 #include <stdio.h>
@@ -17,9 +19,41 @@ static const char *VIGNETTE =
     "    return make_float4(s.x * k, s.y * k, s.z * k, s.w);\n"
     "}\n";
 
+/* (tests/user_shader_sources_affine.py carries the same text as ROTATE) */
+static const char *ROTATE =
+    "#define SMR_HAS_VERTEX_AFFINE\n"
+    "__device__ smr_affine smr_vertex_affine(const smr_shader_in &in, int plane_id) {\n"
+    "    smr_affine m = {1.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f};\n"
+    "    if (plane_id != in.texture_count - 1) return m;\n"
+    "    const uint2 d = smr_dimensions(in, plane_id);\n"
+    "    const float W = (float)in.output_resolution.x, H = (float)in.output_resolution.y;\n"
+    "    const float fit = fminf(W / (float)d.x, H / (float)d.y) * 0.6f;\n"
+    "    const float hw = 0.5f * fit * (float)d.x, hh = 0.5f * fit * (float)d.y;  // the plane's half extent in pixels\n"
+    "    const float c = cosf(in.time), s = sinf(in.time);\n"
+    "    m.xx = 2.0f * hw * c / W; m.xy = -2.0f * hh * s / W;\n"
+    "    m.yx = 2.0f * hw * s / H; m.yy = 2.0f * hh * c / H;\n"
+    "    return m;\n"
+    "}\n"
+    "__device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float2 position) {\n"
+    "    const uint2 d = smr_dimensions(in, plane_id);\n"
+    "    if (plane_id != in.texture_count - 1) {\n"
+    "        int band = (int)(uv.x * 8.0f);\n"
+    "        if (band > (int)d.x - 1) band = (int)d.x - 1;\n"
+    "        return smr_load(in, plane_id, band, 0);\n"
+    "    }\n"
+    "    int tx = (int)floorf(uv.x * (float)d.x), ty = (int)floorf(uv.y * (float)d.y);\n"
+    "    if (tx > (int)d.x - 1) tx = (int)d.x - 1;\n"
+    "    if (ty > (int)d.y - 1) ty = (int)d.y - 1;\n"
+    "    return smr_load(in, plane_id, tx, ty);\n"
+    "}\n";
+
 static const char *SCENE =
     "{\"type\":\"shader\",\"shader_id\":\"vignette\",\"resolution\":{\"width\":640,\"height\":360},"
     "\"shader_param\":{\"type\":\"f32\",\"value\":0.8},\"children\":[{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
+
+static const char *SPIN_SCENE =
+    "{\"type\":\"shader\",\"shader_id\":\"rotate\",\"resolution\":{\"width\":640,\"height\":360},"
+    "\"children\":[{\"type\":\"input_stream\",\"input_id\":\"palette\"},{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
 
 int main(void) {
     /* host only: compile, show what the compiler said */
@@ -34,17 +68,27 @@ int main(void) {
     size_t code_size = 0;
     smr_shader_program_code(prog, &code, &code_size);
     printf("vignette: %zu bytes of gfx950 code\n", code_size);
+    smr_shader_program *spin = NULL;
+    rc = smr_shader_program_create(ROTATE, &spin);
+    if (rc != SMR_OK) {
+        fprintf(stderr, "the rotating shader did not compile (%d):\n%s\n", rc, spin ? smr_shader_program_log(spin) : "");
+        smr_shader_program_destroy(spin);
+        smr_shader_program_destroy(prog);
+        return 1;
+    }
 
     smr_ctx *ctx = NULL;
     if (smr_ctx_create(0, SMR_MODE_GPU_OPTIMIZED, SMR_DEFAULT_MAX_LAYOUTS, NULL, &ctx) != SMR_OK) {
         fprintf(stderr, "no HIP device\n");
+        smr_shader_program_destroy(spin);
         smr_shader_program_destroy(prog);
         return 2;
     }
     smr_renderer *r = NULL;
     int status = 1;
-    smr_frame cam;
+    smr_frame cam, palette;
     memset(&cam, 0, sizeof(cam));
+    memset(&palette, 0, sizeof(palette));
     if (smr_renderer_create(ctx, -1, &r) != 0) goto out;
     if (smr_renderer_register_input(r, "cam") != 0 || smr_renderer_register_shader_program(r, "vignette", prog) != 0 ||
         smr_renderer_update_scene(r, "out", 640, 360, SMR_FRAME_RGBA, SCENE) != 0) {
@@ -72,12 +116,45 @@ int main(void) {
         smr_shader_program_launches(prog, &launches);
         printf("centre %u, corner %u, launches %llu\n", got[(180 * 640 + 320) * 4], got[0], (unsigned long long)launches);
         status = got[(180 * 640 + 320) * 4] > got[0] && launches == 1 ? 0 : 1;
+
+        /* the same output with the rotating shader: an 8 x 1 palette strip behind the camera picture, 0.7 s into the turn */
+        static const uint8_t strip[8][4] = {{255, 0, 0, 255},   {255, 128, 0, 255}, {255, 255, 0, 255}, {0, 255, 0, 255},
+                                            {0, 255, 255, 255}, {0, 0, 255, 255},   {128, 0, 255, 255}, {255, 0, 255, 255}};
+        const void *strip_planes[3] = {strip, NULL, NULL};
+        if (status != 0 || smr_frame_create(ctx, SMR_FRAME_RGBA, 8, 1, &palette) != SMR_OK) {
+            status = 1;
+            free(got);
+            goto out;
+        }
+        smr_frame_upload(ctx, &palette, strip_planes);
+        status = 1;
+        if (smr_renderer_register_input(r, "palette") != 0 || smr_renderer_register_shader_program(r, "rotate", spin) != 0 ||
+            smr_renderer_update_scene(r, "out", 640, 360, SMR_FRAME_RGBA, SPIN_SCENE) != 0) {
+            fprintf(stderr, "%s\n", smr_renderer_last_error(r));
+            free(got);
+            goto out;
+        }
+        smr_input_frame both[2] = {{"cam", &cam, 700000000}, {"palette", &palette, 700000000}};
+        if (smr_renderer_render(r, 700000000, both, 2, out, 1, &n) != 0 || n != 1) {
+            fprintf(stderr, "%s\n", smr_renderer_last_error(r));
+            free(got);
+            goto out;
+        }
+        smr_frame_download(out[0].ctx, out[0].frame, dst);
+        smr_shader_program_launches(spin, &launches);
+        const uint8_t *corner = got, *centre = got + (180 * 640 + 320) * 4;
+        printf("rotating: corner %u %u %u, centre %u %u %u, launches %llu\n", corner[0], corner[1], corner[2], centre[0], centre[1], centre[2],
+               (unsigned long long)launches);
+        /* the corner is the palette's first band, the centre the camera picture */
+        status = corner[0] == 255 && corner[1] == 0 && corner[2] == 0 && centre[1] > 0 && launches == 1 ? 0 : 1;
         free(got);
     }
 out:
     if (r) smr_renderer_destroy(r);
     smr_frame_destroy(ctx, &cam);
+    smr_frame_destroy(ctx, &palette);
     smr_ctx_destroy(ctx);
+    smr_shader_program_destroy(spin);
     smr_shader_program_destroy(prog); /* after the renderer it was registered in */
     return status;
 }

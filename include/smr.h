@@ -444,24 +444,43 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  *     __device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float2 position);
  *     // optional, announced with `#define SMR_HAS_VERTEX` at the top of the source:
  *     __device__ smr_plane smr_vertex(const smr_shader_in &in, int plane_id);
+ *     // or, announced with `#define SMR_HAS_VERTEX_AFFINE` instead:
+ *     __device__ smr_affine smr_vertex_affine(const smr_shader_in &in, int plane_id);
  * The node's semantics are those of the built-in kernels (the same kernel with the user's functions in place of the built-in switch):
  * the target is cleared to transparent, one plane per source is drawn in order (plane_id 0 .. texture_count - 1; one plane with
  * plane_id -1 when the node has no children), every plane blended premultiplied-alpha OVER and stored to the RGBA8 target before the
  * next.  smr_fragment gets the fragment's tex_coords `uv` within the plane and its pixel-centre `position` (@builtin(position).xy) and
  * returns premultiplied RGBA in the target's blending space (linear light in SMR_MODE_GPU_OPTIMIZED, unorm values in
  * SMR_MODE_CPU_OPTIMIZED).  smr_vertex returns smr_plane {sx, sy, cx, cy}: the unit quad's corners go to clip-space position * (sx, sy) +
- * (cx, cy).  The vertex stage is an axis-aligned scale + translate and nothing else: rotated, sheared or otherwise deformed planes are
- * NOT expressible (a plane with sx <= 0 or sy <= 0 covers nothing).  Without smr_vertex every plane covers the target.
+ * (cx, cy); a plane with sx <= 0 or sy <= 0 covers nothing.  smr_vertex_affine returns smr_affine {xx, xy, yx, yy, cx, cy}: corner
+ * (px, py) of the unit quad, px, py in {-1, +1}, goes to clip space X = xx * px + xy * py + cx, Y = yx * px + yy * py + cy — a 2 x 2
+ * matrix and a translation, so any parallelogram is expressible: rotated, sheared, scaled.  Still NOT expressible: perspective (there is
+ * no w) and per-vertex attributes (the four corners carry nothing but their position; uv is the position within the quad).  A pixel
+ * belongs to the plane when its centre, taken back into the quad (qx, qy) = M^-1 (X - cx, Y - cy) in f32, has -1 <= qx < 1 and
+ * -1 < qy <= 1: a centre exactly on an edge belongs to the plane whose left / top edge (in quad space) it is; uv = ((qx + 1) / 2,
+ * (1 - qy) / 2), position stays the pixel centre.  With xy == 0 and yx == 0 the plane IS smr_plane {xx, yy, cx, cy}, byte for byte,
+ * the rule for sx, sy <= 0 included: a half turn written with exact zeros, {-a, 0, 0, -b}, is NOT drawn although its det is positive
+ * (a half turn by sinf / cosf, whose xy and yx are tiny but not zero, is) — write it as {a, 0, 0, b} and flip in the fragment (sample
+ * at 1 - u, 1 - v).  Otherwise det = xx * yy - xy * yx decides: a plane whose det is zero, NaN or infinite covers
+ * nothing, and neither does a MIRRORED plane (det < 0) — the reference draws the quad with front_face Ccw and cull_mode Some(Back)
+ * (smelter-render/src/wgpu/common_pipeline.rs:104-107, the pipeline transformations/shader/pipeline.rs:63 creates), so a plane whose
+ * winding is reversed is culled there too; mirror a picture in the fragment (sample at 1 - u) instead.  A source that defines both
+ * SMR_HAS_VERTEX and SMR_HAS_VERTEX_AFFINE does not compile ("#error": one vertex stage per shader; smr_shader_program_create
+ * returns SMR_ERR_INVALID, the message is in smr_shader_program_log).  Without a vertex stage every plane covers the target.
  * What a shader may use (the library puts it in front of the source):
  *     in.time (seconds, float)   in.output_resolution (uint2)   in.texture_count (int)          BaseShaderParameters (base_params.rs:7-12)
  *     float4 smr_sample(in, i, u, v)        source i through the linear clamp-to-edge sampler, decoded to the blending space;
  *                                           (0, 0, 0, 0) when i is out of range or the source is absent
+ *     uint2 smr_dimensions(in, i)           textureDimensions: source i's width and height; (0, 0) when i is out of range or absent
+ *     float4 smr_load(in, i, x, y)          textureLoad, level 0: exactly texel (x, y) of source i, unfiltered, decoded like a texel of
+ *                                           smr_sample; (0, 0, 0, 0) when i is out of range, the source is absent or (x, y) outside it
  *     T smr_param<T>(in)   const unsigned char *smr_param_bytes(in)   unsigned smr_param_size(in)
  *                                           the @group(1) uniform: the shader_param's values in order, little endian, no padding
  *                                           (ShaderParam::to_bytes); bytes behind smr_param_size read 0
  *     float smr_smoothstep(e0, e1, x)       WGSL smoothstep;  make_float2 / make_float4 and the HIP device math library (sqrtf, sinf, ...)
- * A shader never holds a pointer into a surface: every access goes through smr_sample, which clamps — it cannot read or write outside
- * its sources and target.  It is compiled with the library's own options (--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off):
+ * A shader never holds a pointer into a surface, and that stays true with smr_load: every access goes through smr_sample, which
+ * clamps, or smr_load, which answers (0, 0, 0, 0) outside the source without reading — it cannot read or write outside its sources
+ * and target.  It is compiled with the library's own options (--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off):
  * every multiply and add is rounded on its own, as in the built-in kernels.  Compiling takes of the order of a second (DESIGN.md
  * section 3e): register shaders off the render thread. */
 typedef struct smr_shader_program smr_shader_program;
@@ -641,7 +660,8 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      (the environment is read by laboratory builds only).
  *      Added since, without a new version (additions only: nothing a version-2 host calls changed): SMR_KERNEL_MOVE_RECTS (counter slot 8),
  *      smr_renderer_add_shard, smr_renderer_input_ctx; user shaders (smr_shader_program_*, smr_user_shader,
- *      smr_renderer_register_shader_source / _program).
+ *      smr_renderer_register_shader_source / _program); in the user-shader language, no new C symbol: the affine vertex stage
+ *      (smr_affine, smr_vertex_affine under SMR_HAS_VERTEX_AFFINE), smr_load and smr_dimensions.
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2
