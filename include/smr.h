@@ -235,7 +235,8 @@ typedef enum smr_kernel_id {
     SMR_KERNEL_COMPOSE_OUTPUT = 6,   /* k_compose_output: layout shader + output conversion */
     SMR_KERNEL_APPLY_LAYOUTS = 7,    /* k_apply_layouts: the general compositor */
     SMR_KERNEL_MOVE_RECTS = 8,       /* k_move_rects: the local gather's transport (smr_gather_tiles), one launch per sending context and 16 rectangles */
-    SMR_KERNEL_COUNT_ = 9
+    SMR_KERNEL_INGEST_WAVE_DIRECT = 9, /* k_ingest_wave launches that carry a direct-output job (SMR_OPT_DIRECT_OUTPUT: the kernel stores Y'CbCr into the output frame) */
+    SMR_KERNEL_COUNT_ = 10
 } smr_kernel_id;
 SMR_API int smr_debug_kernel_launches(const smr_ctx *ctx, uint32_t kernel, uint64_t *count);
 
@@ -250,7 +251,17 @@ SMR_API int smr_surface_create(smr_ctx *ctx, uint32_t w, uint32_t h, uint32_t fo
  *   - RGBA8 / RGBA16F surfaces handed to the resampler or the compositor: whole 16-byte groups inside a row's pitch — the allocation must
  *     back every row out to the pitch rounded down to 16 bytes, the LAST ROW TOO.
  * Planes the library allocates itself (smr_surface_create / smr_frame_create: every allocation ends with 16 spare bytes) take the plain
- * converter. */
+ * converter.
+ * What the library WRITES of a wrapped surface — a node texture, a tile, the planes of an output frame, an out_rgba target, whichever
+ * entry point it is handed to as a destination: the w x h texels (w * bytes per texel in each of the h rows) and NO OTHER BYTE.  Not the
+ * bytes between a row's last texel and the pitch, not a byte before the base pointer, not a byte after the last row's last texel: the
+ * destination may be a window inside a larger allocation (an encoder surface inside a pool, a region of a shared picture) whose
+ * "padding" is somebody else's pixels.  Kernels that store in groups (four pixels, 4 x 2 blocks, 16-byte tile stores) narrow the ragged
+ * last group's store; routes whose stores need an alignment the surface does not have fall back to kernels that produce the same bytes.
+ * smr_surface_clear and the uploads are part of it: they touch the texels' bytes of each row, not the rows out to the pitch.
+ * Held on the device by tests/test_gpu_write_footprint.py (tight / slack / window geometries; every entry point that takes a destination
+ * surface or frame except smr_gather_tiles, which the sharded compositor uses between tiles the library allocated, and the renderer, which
+ * allocates its own outputs) and on the CPU emulator by guard mode 3 of tests/emu. */
 SMR_API int smr_surface_wrap(smr_ctx *ctx, void *dptr, size_t pitch, uint32_t w, uint32_t h, uint32_t format,
                              smr_surface **out);
 SMR_API void smr_surface_destroy(smr_ctx *ctx, smr_surface *s);
@@ -659,6 +670,7 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      SMR_CONVERT_GENERAL / SMR_DISABLE_FUSED / SMR_COMPOSE_SELECT environment knobs are smr_ctx_set_option options in a product build
  *      (the environment is read by laboratory builds only).
  *      Added since, without a new version (additions only: nothing a version-2 host calls changed): SMR_KERNEL_MOVE_RECTS (counter slot 8),
+ *      SMR_KERNEL_INGEST_WAVE_DIRECT (counter slot 9),
  *      smr_renderer_add_shard, smr_renderer_input_ctx; user shaders (smr_shader_program_*, smr_user_shader,
  *      smr_renderer_register_shader_source / _program); in the user-shader language, no new C symbol: the affine vertex stage
  *      (smr_affine, smr_vertex_affine under SMR_HAS_VERTEX_AFFINE), smr_load and smr_dimensions.

@@ -430,7 +430,8 @@ int smr_surface_download(smr_ctx *ctx, const smr_surface *s, void *host, size_t 
 int smr_surface_clear(smr_ctx *ctx, smr_surface *s) {
     SMR_ENTER(ctx);
     if (!ctx || !s) return SMR_ERR_INVALID;
-    SMR_HIP(ctx, hipMemsetAsync(s->ptr, 0, s->pitch * s->h, ctx->stream));
+    // (the texels only: a wrapped surface's padding is the caller's — smr_surface_wrap's WRITE contract, include/smr.h)
+    SMR_HIP(ctx, hipMemset2DAsync(s->ptr, s->pitch, 0, (size_t)s->w * bytes_per_px(s->fmt), s->h, ctx->stream));
     return SMR_OK;
 }
 

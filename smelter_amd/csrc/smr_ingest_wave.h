@@ -1696,6 +1696,11 @@ int launch_wave(smr_ctx *ctx, std::vector<WJob> &jobs, const MDirect *direct = n
         else if (sa) ki = 300 + sa_i;
         else if (rgba) ki += f16 ? (alpha ? 250 : 200) : alpha ? 400 : rgb12 ? (direct ? 650 : 600) : (direct ? 150 : 100);
         ctx->kernel_launches[rgba ? SMR_KERNEL_INGEST_WAVE_RGBA : SMR_KERNEL_INGEST_WAVE]++;  // (slot 0: the builds that read the frame's planes)
+        if (direct) {  // (a job smr_render_layouts marked: its copy tiles leave this launch as Y'CbCr in the output frame)
+            bool marked = false;
+            for (size_t j = 0; j < nj; j++) marked = marked || jobs[j0 + j].layer >= 0;
+            if (marked) ctx->kernel_launches[SMR_KERNEL_INGEST_WAVE_DIRECT]++;
+        }
         // (the narrow class keeps its pass-1 band in registers: no LDS for it)
         args.b_bytes = (cls_nks && SMR_WAVE_PIPE && SMR_WAVE_B_REGS) ? 0 : w_band_bytes(cls_nks ? cls_nks : nks_max);
         // (node-texture builds stage nothing: the area behind the band only holds the alpha builds' 1 KB table)

@@ -61,13 +61,19 @@ struct Surface {
 };
 // rows on the allocator's 256-byte pitch, or (emu_set_guard(.., 1)) on the smallest pitch a surface of that width can have:
 // `align`-byte multiples
+// (a destination — tight == nullptr, an output plane — in guard mode 3: + 32 bytes of padding per row, the buffer filled from the seeded pattern)
 void make_surface(Surface &s, const u8 *tight, int w, int h, int bpp, u32 align, u8 fill) {
     u32 pitch = (u32)(((size_t)w * bpp + 255) & ~(size_t)255);
     if (emu_min_pitch) pitch = (u32)(((size_t)w * bpp + align - 1) & ~(size_t)(align - 1));
+    if (emu_min_pitch && !tight) pitch = emu_dst_pitch(pitch);
     s.buf.alloc((size_t)pitch * h, fill, align);
+    if (!tight) emu_pad_fill(s.buf.ptr, pitch, h, 0x0a7 + (u32)bpp * 16 + align);
     if (tight)
         for (int y = 0; y < h; y++) memcpy(s.buf.ptr + (size_t)y * pitch, tight + (size_t)y * w * bpp, (size_t)w * bpp);
     s.view.ptr = s.buf.ptr; s.view.pitch = pitch; s.view.w = w; s.view.h = h;
+}
+int check_padding(const Surface &s, int bpp, u32 align, const char *what) {
+    return emu_pad_check(s.buf.ptr, s.view.pitch, (size_t)s.view.w * bpp, s.view.h, 0x0a7 + (u32)bpp * 16 + align, what);
 }
 void read_back(const Surface &s, u8 *tight, int bpp) {
     for (int y = 0; y < s.view.h; y++) memcpy(tight + (size_t)y * s.view.w * bpp, s.buf.ptr + (size_t)y * s.view.pitch, (size_t)s.view.w * bpp);
@@ -161,6 +167,17 @@ extern "C" int emu_compose(const smr_layout *layouts, int n, int n_sources, cons
     else if (nv == 1) { if (big) EMU_COMPOSE(1, true); else EMU_COMPOSE(1, false); }
     else { if (big) EMU_COMPOSE(2, true); else EMU_COMPOSE(2, false); }
 #undef EMU_COMPOSE
+    if (nv == 2) {
+        if (int rc = check_padding(p0, 4, 16, "RGBA8 output")) return rc;
+    } else {
+        if (int rc = check_padding(p0, 1, 4, "Y plane")) return rc;
+        if (nv == 1) {
+            if (int rc = check_padding(p1, 2, 4, "UV plane")) return rc;
+        } else {
+            if (int rc = check_padding(p1, 1, 2, "U plane")) return rc;
+            if (int rc = check_padding(p2, 1, 2, "V plane")) return rc;
+        }
+    }
     if (nv == 2) read_back(p0, out0, 4);
     else {
         read_back(p0, out0, 1);

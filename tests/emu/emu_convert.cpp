@@ -53,9 +53,10 @@ u32 chroma_need(int w, int nv12) {
     return nv12 ? ((2u * (cw - 3u)) & ~3u) + 12u : ((cw - 3u) & ~3u) + 8u;
 }
 u32 node_pitch(int w, int rgb12) {
-    if (emu_min_pitch) return rgb12 ? (u32)((3 * w + 15) & ~15) : (u32)w * 4;
+    if (emu_min_pitch) return emu_dst_pitch(rgb12 ? (u32)((3 * w + 15) & ~15) : (u32)w * 4);  // (guard mode 3: + 32 bytes of watched padding)
     return rgb12 ? (u32)((3 * w + 255) & ~255) : (u32)w * 4;
 }
+size_t node_row_bytes(int w, int rgb12) { return (size_t)w * (rgb12 ? 3 : 4); }
 
 }  // namespace
 
@@ -69,6 +70,7 @@ extern "C" int emu_convert_420_run(const u8 *y, const u8 *u, const u8 *v, int w,
     const u32 dpitch = node_pitch(w, rgb12);
     GuardBuf dst;
     dst.alloc((size_t)dpitch * h, 0, 16);
+    emu_pad_fill(dst.ptr, dpitch, h, 0xc0de);
     ConvJob J;
     memset(&J, 0, sizeof(J));
     J.yp = py.view; J.up = pu.view; J.vp = nv12 ? pu.view : pv.view;
@@ -99,10 +101,11 @@ extern "C" int emu_convert_420_run(const u8 *y, const u8 *u, const u8 *v, int w,
             }
 #undef EMU_CV
         }
+    if (int rc = emu_pad_check(dst.ptr, dpitch, node_row_bytes(w, rgb12), h, 0xc0de, rgb12 ? "RGB12 node" : "RGBA8 node")) return rc;
     if (rgb12) {
         for (int r = 0; r < h; r++) memcpy(out + (size_t)r * 3 * w, dst.ptr + (size_t)r * dpitch, (size_t)3 * w);
     } else {
-        memcpy(out, dst.ptr, (size_t)w * 4 * h);
+        for (int r = 0; r < h; r++) memcpy(out + (size_t)r * 4 * w, dst.ptr + (size_t)r * dpitch, (size_t)4 * w);
     }
     return 0;
 }
@@ -131,6 +134,7 @@ extern "C" int emu_convert_420_shares(int n, const u8 *const *ys, const u8 *cons
         if (!nv12) pv[i] = make_plane(vs[i], w / 2, h / 2, 1, 0x3c, need);
         dpitch[i] = node_pitch(w, rgb12s[i]);
         dst[i].alloc((size_t)dpitch[i] * h, 0, 16);
+        emu_pad_fill(dst[i].ptr, dpitch[i], h, 0xc0de + (u32)i);
         ConvJob &J = B.j[i];
         J.yp = py[i].view; J.up = pu[i].view; J.vp = nv12 ? pu[i].view : pv[i].view;
         J.dst.ptr = dst[i].ptr; J.dst.pitch = dpitch[i]; J.dst.w = w; J.dst.h = h;
@@ -154,12 +158,14 @@ extern "C" int emu_convert_420_shares(int n, const u8 *const *ys, const u8 *cons
                 } else if (nv12) cv420_share<true>(B, blk, wv, grid, lane, ylut, nlut);
                 else cv420_share<false>(B, blk, wv, grid, lane, ylut, nlut);
             }
+    for (int i = 0; i < n; i++)
+        if (int rc = emu_pad_check(dst[i].ptr, dpitch[i], node_row_bytes(ws[i], rgb12s[i]), hs[i], 0xc0de + (u32)i, rgb12s[i] ? "RGB12 node" : "RGBA8 node")) return rc;
     for (int i = 0; i < n; i++) {
         const int w = ws[i], h = hs[i];
         if (rgb12s[i]) {
             for (int r = 0; r < h; r++) memcpy(outs[i] + (size_t)r * 3 * w, dst[i].ptr + (size_t)r * dpitch[i], (size_t)3 * w);
         } else {
-            memcpy(outs[i], dst[i].ptr, (size_t)w * 4 * h);
+            for (int r = 0; r < h; r++) memcpy(outs[i] + (size_t)r * 4 * w, dst[i].ptr + (size_t)r * dpitch[i], (size_t)4 * w);
         }
     }
     return 0;

@@ -160,9 +160,10 @@ extern "C" int emu_ingest_wave(const u8 *y, const u8 *u, const u8 *v, int sw, in
     if (rgb12) py.view.w = sw;
     Plane pu = rgba ? py : (nv12 ? make_plane(u, sw / 2, sh / 2, 2) : make_plane(u, sw / 2, sh / 2, 1));
     Plane pv = (nv12 || rgba) ? pu : make_plane(v, sw / 2, sh / 2, 1);
-    const u32 tile_pitch = emu_min_pitch ? (u32)(((size_t)dw * 4 + 15) & ~(size_t)15) : (u32)(((size_t)dw * 4 + 255) & ~(size_t)255);
+    const u32 tile_pitch = emu_min_pitch ? emu_dst_pitch((u32)(((size_t)dw * 4 + 15) & ~(size_t)15)) : (u32)(((size_t)dw * 4 + 255) & ~(size_t)255);  // (guard mode 3: + 32 bytes of watched padding)
     GuardBuf tile;
     tile.alloc((size_t)tile_pitch * dh, 0x5a, 16);
+    emu_pad_fill(tile.ptr, tile_pitch, dh, 0x711e);
     const bool single = specialised == 3;  // one tile per unit (axis 4 bands): windows too wide for a pair; generic builds
     if (single) specialised = 0;
     Band bh = build_band(scale_h, off_h, dw, sw, single ? 4 : 2), bv = build_band(scale_v, off_v, dh, sh, planes ? 5 : 3);
@@ -267,6 +268,7 @@ extern "C" int emu_ingest_wave(const u8 *y, const u8 *u, const u8 *v, int sw, in
         else run_grid(blocks, W_THREADS, lds, [&] { k_ingest_wave<0, 0, 0>(args, tables, lut16); });
     }
 #endif
+    if (int rc = emu_pad_check(tile.ptr, tile_pitch, (size_t)dw * 4, dh, 0x711e, "tile")) return rc;
     for (int yy = 0; yy < dh; yy++) memcpy(dst + (size_t)yy * dw * 4, J.dst.ptr + (size_t)yy * J.dst.pitch, (size_t)dw * 4);
     return 0;
 }

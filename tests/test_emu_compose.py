@@ -252,13 +252,15 @@ def test_compositor_never_leaves_its_surfaces(emu):
     """The memory contract of include/smr.h for wave B: the scenes above once more in child processes with every source texture, output plane,
     layout / mask / class / list array in an allocation of exactly its size — surfaces on the smallest pitch their width allows — ending at
     (mode 1) or starting behind (mode 2) an unmapped page: a 16-byte texel load past a tile's last row, a Y'CbCr store beyond a plane of an
-    output whose width is 2 mod 4, a layout record read past the list would kill the child."""
+    output whose width is 2 mod 4, a layout record read past the list would kill the child.  Mode 3 (tests/emu/emu_guard.h): every output
+    plane on that pitch + 32, filled from a seeded pattern, its row padding compared after the launch — store_yuv_block's `half` stores and
+    the RGBA8 output's 16-byte stores writing past a row's last texel fail the child with the plane, row and byte."""
     if os.environ.get("SMR_EMU_GUARD"):
         pytest.skip("this is the inner run")
     children = {mode: subprocess.Popen([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-p", "no:cacheprovider"],
                                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=dict(os.environ, SMR_EMU_GUARD=str(mode)), cwd=ROOT)
-                for mode in (1, 2)}
+                for mode in (1, 2, 3)}
     for mode, child in children.items():
         out, err = child.communicate(timeout=1500)
-        assert child.returncode == 0, f"guard mode {mode}: rc {child.returncode} (-11 = the kernel left its surfaces)\n{out[-3000:]}\n{err[-2000:]}"
+        assert child.returncode == 0, f"guard mode {mode}: rc {child.returncode} (-11 = the kernel left its surfaces; 'write footprint' = it wrote row padding)\n{out[-3000:]}\n{err[-2000:]}"
         assert " passed" in out

@@ -152,18 +152,21 @@ def test_a_launch_cut_into_equal_shares_writes_the_oracles_bytes(emu, nv, waves)
         assert np.array_equal(got, want), (w, h, waves, int((got != want).sum()))
 
 
-@pytest.mark.parametrize("mode", [1, 2])
+@pytest.mark.parametrize("mode", [1, 2, 3])
 def test_converter_never_leaves_its_planes(emu, mode):
     """The memory contract of include/smr.h (smr_surface_wrap): an allocation covers pitch * h bytes and no kernel touches a byte outside it.
     The tests above once more in a child process, with every plane and node texture exactly pitch * h bytes — on the SMALLEST pitch the host
     code lets through (conv_420_ok: the reach of the last block's dword loads) — ending at (mode 1) or starting behind (mode 2) an unmapped
-    page: a load or store outside the allocation kills the child.  Prefetches included: a run requests nothing behind its last block."""
+    page: a load or store outside the allocation kills the child.  Prefetches included: a run requests nothing behind its last block.
+    Mode 3 is the WRITE half of that contract (tests/emu/emu_guard.h): every node texture on the smallest pitch + 32, the whole buffer filled
+    from a seeded pattern, the row padding compared after the launch — a 16-byte (RGB12: 12-byte) group store that spilled past a row's last
+    texel fails the child with the row and byte (rc -77 of the emulator call, the message on its stderr)."""
     if os.environ.get("SMR_EMU_GUARD") or os.environ.get("SMR_EMU_TIGHT"):
         pytest.skip("this is the inner run")
     env = dict(os.environ, SMR_EMU_GUARD=str(mode))
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-p", "no:cacheprovider", "-k",
                         "block_converter or runs_of_blocks or equal_shares"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=1200)
-    assert r.returncode == 0, f"guard mode {mode}: rc {r.returncode} (-11 = a kernel left its planes)\n{r.stdout[-3000:]}\n{r.stderr[-2000:]}"
+    assert r.returncode == 0, f"guard mode {mode}: rc {r.returncode} (-11 = a kernel left its planes; 'write footprint' = it wrote row padding)\n{r.stdout[-3000:]}\n{r.stderr[-2000:]}"
     assert " passed" in r.stdout
 
 

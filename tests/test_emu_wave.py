@@ -384,14 +384,16 @@ def test_resampler_never_leaves_its_surfaces(emu):
     axis, single-tile units): those tests once more in child processes with node textures, tiles and weight bands of exactly pitch * h
     bytes — node and tile on the SMALLEST pitch can_fuse_wave_rgba lets through (16-byte multiples holding the row rounded up to four
     texels) — ending at (mode 1) or starting behind (mode 2) an unmapped page: a 16-byte load of the last texel group that reached past the
-    row's pitch, a window clamped a row too late, a store beyond the tile would kill the child."""
+    row's pitch, a window clamped a row too late, a store beyond the tile would kill the child.  Mode 3 (tests/emu/emu_guard.h): the tile on
+    that pitch + 32, filled from a seeded pattern, its row padding compared after the launch — store_rows' narrow path for a ragged last
+    group (tile widths of 1, 2, 3 mod 4) writing one texel too many fails the child with the row and byte."""
     import sys
     if os.environ.get("SMR_EMU_GUARD"):
         pytest.skip("this is the inner run")
     children = {mode: subprocess.Popen([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-p", "no:cacheprovider", "-k",
                                         "rgb12 or alpha or rgba16f or single_tile or single_axis"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                                       env=dict(os.environ, SMR_EMU_GUARD=str(mode)), cwd=ROOT) for mode in (1, 2)}
+                                       env=dict(os.environ, SMR_EMU_GUARD=str(mode)), cwd=ROOT) for mode in (1, 2, 3)}
     for mode, child in children.items():
         out, err = child.communicate(timeout=1500)
-        assert child.returncode == 0, f"guard mode {mode}: rc {child.returncode} (-11 = the kernel left its surfaces)\n{out[-3000:]}\n{err[-2000:]}"
+        assert child.returncode == 0, f"guard mode {mode}: rc {child.returncode} (-11 = the kernel left its surfaces; 'write footprint' = it wrote row padding)\n{out[-3000:]}\n{err[-2000:]}"
         assert " passed" in out

@@ -36,15 +36,15 @@ def test_generated_rust_binding_binds_them():
         m = re.search(r"^\+\s*pub fn " + name + r"\(([^)]*)\) -> c_int;", patch, flags=re.M)
         assert m, f"hip/sys.rs does not bind {name}"
         assert len(m.group(1).split(",")) == arity
-    assert "+pub const SMR_KERNEL_MOVE_RECTS: u32 = 8;" in patch and "+pub const SMR_KERNEL_COUNT_: u32 = 9;" in patch
+    assert "+pub const SMR_KERNEL_MOVE_RECTS: u32 = 8;" in patch and "+pub const SMR_KERNEL_COUNT_: u32 = 10;" in patch
 
 
 def test_abi_version_is_still_two_and_the_counter_has_its_slot(lib):
     from smelter_amd import hip
     hdr = open(os.path.join(ROOT, "include", "smr.h")).read()
     assert lib.smr_abi_version() == 2 and "#define SMR_ABI_VERSION 2" in hdr
-    assert re.search(r"SMR_KERNEL_MOVE_RECTS\s*=\s*8\b", hdr) and re.search(r"SMR_KERNEL_COUNT_\s*=\s*9\b", hdr)
-    assert hip.KERNEL_NAMES[8] == "move_rects" and len(hip.KERNEL_NAMES) == 9
+    assert re.search(r"SMR_KERNEL_MOVE_RECTS\s*=\s*8\b", hdr) and re.search(r"SMR_KERNEL_COUNT_\s*=\s*10\b", hdr)
+    assert hip.KERNEL_NAMES[8] == "move_rects" and len(hip.KERNEL_NAMES) == 10  # (slot 9: SMR_KERNEL_INGEST_WAVE_DIRECT, an addition behind it)
     assert "smr_renderer_add_shard" in hdr[hdr.index("#define SMR_ABI_VERSION") - 2500:hdr.index("#define SMR_ABI_VERSION")], "the header's history names the additions"
 
 
