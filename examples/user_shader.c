@@ -2,6 +2,8 @@
  * drawn by a Shader node.  The first shader here is a vignette: source 0 darkened towards the corners, `strength` from the node's
  * shader_param.  The second has an affine vertex stage: its last source turns by in.time radians about the target's centre, its aspect
  * ratio kept (smr_dimensions); outside that plane the target shows eight bands whose colours are the texels of a palette strip (smr_load).
+ * The third has a clip vertex stage (a homogeneous position and tex_coords per vertex of the quad): the same picture as a card turning
+ * about its vertical axis by in.time radians, in perspective; once it has turned its back it is culled and only the bands show.
  *   gcc -std=c11 -Iinclude examples/user_shader.c -o user_shader -Lsmelter_amd -l:libsmr_hip.so -Wl,-rpath,$PWD/smelter_amd -lm
  * Exit codes: 0 ok, 2 no HIP device (the shader was still compiled: that needs none), 1 anything else. */
 #include <stdio.h>
@@ -47,9 +49,43 @@ static const char *ROTATE =
     "    return smr_load(in, plane_id, tx, ty);\n"
     "}\n";
 
+/* (tests/user_shader_sources_clip.py carries the same text as FLIP) */
+static const char *FLIP =
+    "#define SMR_HAS_VERTEX_CLIP\n"
+    "__device__ smr_clip_vertex smr_vertex_clip(const smr_shader_in &in, int plane_id, int vertex_index, float3 position, float2 tex_coords) {\n"
+    "    smr_clip_vertex o;\n"
+    "    o.position = make_float4(position.x, position.y, 0.0f, 1.0f);\n"
+    "    o.tex_coords = tex_coords;\n"
+    "    if (plane_id != in.texture_count - 1) return o;\n"
+    "    const uint2 d = smr_dimensions(in, plane_id);\n"
+    "    const float W = (float)in.output_resolution.x, H = (float)in.output_resolution.y;\n"
+    "    const float fit = fminf(W / (float)d.x, H / (float)d.y) * 0.6f;\n"
+    "    const float sx = fit * (float)d.x / W, sy = fit * (float)d.y / H;  // the card's half extent in clip space\n"
+    "    const float xr = position.x * sx * cosf(in.time), zr = position.x * sx * sinf(in.time);\n"
+    "    const float w = 1.0f + zr / 2.5f;\n"
+    "    o.position = make_float4(xr, position.y * sy, 0.5f * w, w);\n"
+    "    return o;\n"
+    "}\n"
+    "__device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float2 position) {\n"
+    "    const uint2 d = smr_dimensions(in, plane_id);\n"
+    "    if (plane_id != in.texture_count - 1) {\n"
+    "        int band = (int)(uv.x * 8.0f);\n"
+    "        if (band > (int)d.x - 1) band = (int)d.x - 1;\n"
+    "        return smr_load(in, plane_id, band, 0);\n"
+    "    }\n"
+    "    int tx = (int)floorf(uv.x * (float)d.x), ty = (int)floorf(uv.y * (float)d.y);\n"
+    "    if (tx > (int)d.x - 1) tx = (int)d.x - 1;\n"
+    "    if (ty > (int)d.y - 1) ty = (int)d.y - 1;\n"
+    "    return smr_load(in, plane_id, tx, ty);\n"
+    "}\n";
+
 static const char *SCENE =
     "{\"type\":\"shader\",\"shader_id\":\"vignette\",\"resolution\":{\"width\":640,\"height\":360},"
     "\"shader_param\":{\"type\":\"f32\",\"value\":0.8},\"children\":[{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
+
+static const char *FLIP_SCENE =
+    "{\"type\":\"shader\",\"shader_id\":\"flip\",\"resolution\":{\"width\":640,\"height\":360},"
+    "\"children\":[{\"type\":\"input_stream\",\"input_id\":\"palette\"},{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
 
 static const char *SPIN_SCENE =
     "{\"type\":\"shader\",\"shader_id\":\"rotate\",\"resolution\":{\"width\":640,\"height\":360},"
@@ -76,10 +112,20 @@ int main(void) {
         smr_shader_program_destroy(prog);
         return 1;
     }
+    smr_shader_program *flip = NULL;
+    rc = smr_shader_program_create(FLIP, &flip);
+    if (rc != SMR_OK) {
+        fprintf(stderr, "the card shader did not compile (%d):\n%s\n", rc, flip ? smr_shader_program_log(flip) : "");
+        smr_shader_program_destroy(flip);
+        smr_shader_program_destroy(spin);
+        smr_shader_program_destroy(prog);
+        return 1;
+    }
 
     smr_ctx *ctx = NULL;
     if (smr_ctx_create(0, SMR_MODE_GPU_OPTIMIZED, SMR_DEFAULT_MAX_LAYOUTS, NULL, &ctx) != SMR_OK) {
         fprintf(stderr, "no HIP device\n");
+        smr_shader_program_destroy(flip);
         smr_shader_program_destroy(spin);
         smr_shader_program_destroy(prog);
         return 2;
@@ -147,6 +193,21 @@ int main(void) {
                (unsigned long long)launches);
         /* the corner is the palette's first band, the centre the camera picture */
         status = corner[0] == 255 && corner[1] == 0 && corner[2] == 0 && centre[1] > 0 && launches == 1 ? 0 : 1;
+
+        /* the same two inputs with the card shader, 0.7 s into the turn: the card still faces the eye */
+        if (status != 0 || smr_renderer_register_shader_program(r, "flip", flip) != 0 ||
+            smr_renderer_update_scene(r, "out", 640, 360, SMR_FRAME_RGBA, FLIP_SCENE) != 0 ||
+            smr_renderer_render(r, 700000000, both, 2, out, 1, &n) != 0 || n != 1) {
+            if (status == 0) fprintf(stderr, "%s\n", smr_renderer_last_error(r));
+            status = 1;
+            free(got);
+            goto out;
+        }
+        smr_frame_download(out[0].ctx, out[0].frame, dst);
+        smr_shader_program_launches(flip, &launches);
+        printf("card: corner %u %u %u, centre %u %u %u, launches %llu\n", corner[0], corner[1], corner[2], centre[0], centre[1], centre[2],
+               (unsigned long long)launches);
+        status = corner[0] == 255 && corner[1] == 0 && corner[2] == 0 && centre[1] > 0 && launches == 1 ? 0 : 1;
         free(got);
     }
 out:
@@ -154,6 +215,7 @@ out:
     smr_frame_destroy(ctx, &cam);
     smr_frame_destroy(ctx, &palette);
     smr_ctx_destroy(ctx);
+    smr_shader_program_destroy(flip);
     smr_shader_program_destroy(spin);
     smr_shader_program_destroy(prog); /* after the renderer it was registered in */
     return status;

@@ -457,6 +457,8 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  *     __device__ smr_plane smr_vertex(const smr_shader_in &in, int plane_id);
  *     // or, announced with `#define SMR_HAS_VERTEX_AFFINE` instead:
  *     __device__ smr_affine smr_vertex_affine(const smr_shader_in &in, int plane_id);
+ *     // or, announced with `#define SMR_HAS_VERTEX_CLIP` instead (the clip vertex stage: below):
+ *     __device__ smr_clip_vertex smr_vertex_clip(const smr_shader_in &in, int plane_id, int vertex_index, float3 position, float2 tex_coords);
  * The node's semantics are those of the built-in kernels (the same kernel with the user's functions in place of the built-in switch):
  * the target is cleared to transparent, one plane per source is drawn in order (plane_id 0 .. texture_count - 1; one plane with
  * plane_id -1 when the node has no children), every plane blended premultiplied-alpha OVER and stored to the RGBA8 target before the
@@ -465,8 +467,8 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  * SMR_MODE_CPU_OPTIMIZED).  smr_vertex returns smr_plane {sx, sy, cx, cy}: the unit quad's corners go to clip-space position * (sx, sy) +
  * (cx, cy); a plane with sx <= 0 or sy <= 0 covers nothing.  smr_vertex_affine returns smr_affine {xx, xy, yx, yy, cx, cy}: corner
  * (px, py) of the unit quad, px, py in {-1, +1}, goes to clip space X = xx * px + xy * py + cx, Y = yx * px + yy * py + cy — a 2 x 2
- * matrix and a translation, so any parallelogram is expressible: rotated, sheared, scaled.  Still NOT expressible: perspective (there is
- * no w) and per-vertex attributes (the four corners carry nothing but their position; uv is the position within the quad).  A pixel
+ * matrix and a translation, so any parallelogram is expressible: rotated, sheared, scaled; perspective and per-vertex tex_coords need the
+ * clip vertex stage below.  Still NOT expressible: varyings other than tex_coords, compute passes, raw surface access, WGSL text.  A pixel
  * belongs to the plane when its centre, taken back into the quad (qx, qy) = M^-1 (X - cx, Y - cy) in f32, has -1 <= qx < 1 and
  * -1 < qy <= 1: a centre exactly on an edge belongs to the plane whose left / top edge (in quad space) it is; uv = ((qx + 1) / 2,
  * (1 - qy) / 2), position stays the pixel centre.  With xy == 0 and yx == 0 the plane IS smr_plane {xx, yy, cx, cy}, byte for byte,
@@ -478,6 +480,33 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  * winding is reversed is culled there too; mirror a picture in the fragment (sample at 1 - u) instead.  A source that defines both
  * SMR_HAS_VERTEX and SMR_HAS_VERTEX_AFFINE does not compile ("#error": one vertex stage per shader; smr_shader_program_create
  * returns SMR_ERR_INVALID, the message is in smr_shader_program_log).  Without a vertex stage every plane covers the target.
+ *   The clip vertex stage (SMR_HAS_VERTEX_CLIP) is the reference's: it is called once for each of the four vertices of every plane's quad
+ * (smelter-render/src/wgpu/common_pipeline/plane.rs:6-28; vertex_index 0..3, `position` / `tex_coords` = (1, -1, 0) / (1, 1), (1, 1, 0) /
+ * (1, 0), (-1, 1, 0) / (0, 0), (-1, -1, 0) / (0, 1)) and returns smr_clip_vertex {float4 position; float2 tex_coords;}: the homogeneous
+ * clip-space position (x, y, z, w) and the one varying.  It may use what smr_fragment may use except smr_sample (WGSL has no textureSample
+ * outside the fragment stage): smr_load, smr_dimensions, the parameters, in.*.  Any other varying is not expressible.  Defining it together
+ * with SMR_HAS_VERTEX or SMR_HAS_VERTEX_AFFINE is the same "#error" (one vertex stage per shader, SMR_ERR_INVALID, the message in the log).
+ * smr_fragment keeps its signature: uv is the interpolated tex_coords, position the pixel centre.  The quad is drawn as the triangles
+ * (0, 1, 2) then (2, 3, 0) by 2-D homogeneous rasterisation — no clipping step, no division before coverage.  With p_k = (x_k, y_k, w_k)
+ * of vertex k, for triangle (i, j, k):
+ *   - edge coefficients (a, b, c)_i = p_j x p_k, and cyclic: a_i = y_j w_k - w_j y_k, b_i = w_j x_k - x_j w_k, c_i = x_j y_k - y_j x_k.  The
+ *     shared diagonal is p_2 x p_0 in the first triangle and p_0 x p_2 in the second: exact negations of each other.
+ *   - D = det[p_i p_j p_k] = (x_i a_i + y_i b_i) + w_i c_i.  The triangle is drawn only if D > 0 and finite: D <= 0 is a back face (the
+ *     reference culls with front_face Ccw, cull_mode Back), an edge-on or degenerate plane; NaN or infinite D, or any interpolation
+ *     coefficient below that is not finite (a NaN or infinity in z or tex_coords, products that overflow), covers nothing.  The identity
+ *     stage gives D = 4 for both triangles.
+ *   - with the pixel centre (X, Y) in clip space (X = (x + 0.5) / W * 2 - 1, Y = 1 - (y + 0.5) / H * 2), E_i = (a_i X + b_i Y) + c_i.  The
+ *     pixel is covered if every E_i is > 0, or == 0 on an inclusive edge: a_i > 0, or a_i == 0 and b_i < 0 — the top-left rule with Y
+ *     pointing up, which agrees with the half-open rule of smr_plane; a centre on the diagonal belongs to exactly one triangle.  With D > 0
+ *     the covered region is exactly the part of the triangle with w > 0: a vertex behind the eye (w <= 0) needs no special case.
+ *   - depth clip, 0 <= z <= w as wgpu clips: the pixel is dropped unless sum E_i z_i >= 0 and sum E_i (w_i - z_i) >= 0.
+ *   - uv = sum E_i tex_coords_i / sum E_i: perspective-correct (E_i / sum E are the barycentrics on the triangle in clip space).
+ *   The kernel evaluates this in f32, every operation rounded on its own, in this order: the cross products as written; for each attribute
+ *   t in {u, v, z, w - z} (w - z rounded first) the plane A_t = (a_0 t_0 + a_1 t_1) + a_2 t_2, B_t and C_t likewise from b and c, once per
+ *   triangle; per pixel E_i as above, the sums as (A_t X + B_t Y) + C_t, sum E = (E_0 + E_1) + E_2, u and v by one division each.  A pixel
+ *   covered by both triangles (possible only with contrived w: with w = 1 the second triangle of a folded quad is back-facing) is blended
+ *   once per triangle in index order.  Everything after coverage is as for the other stages: premultiplied OVER, the store to the RGBA8
+ *   target, the read back before the next triangle, the final transparent store.
  * What a shader may use (the library puts it in front of the source):
  *     in.time (seconds, float)   in.output_resolution (uint2)   in.texture_count (int)          BaseShaderParameters (base_params.rs:7-12)
  *     float4 smr_sample(in, i, u, v)        source i through the linear clamp-to-edge sampler, decoded to the blending space;
@@ -673,7 +702,8 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      SMR_KERNEL_INGEST_WAVE_DIRECT (counter slot 9),
  *      smr_renderer_add_shard, smr_renderer_input_ctx; user shaders (smr_shader_program_*, smr_user_shader,
  *      smr_renderer_register_shader_source / _program); in the user-shader language, no new C symbol: the affine vertex stage
- *      (smr_affine, smr_vertex_affine under SMR_HAS_VERTEX_AFFINE), smr_load and smr_dimensions.
+ *      (smr_affine, smr_vertex_affine under SMR_HAS_VERTEX_AFFINE), smr_load and smr_dimensions; the clip vertex stage (smr_clip_vertex,
+ *      smr_vertex_clip under SMR_HAS_VERTEX_CLIP: perspective and per-vertex tex_coords, drawn as two triangles).
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

@@ -2,7 +2,7 @@
 // A program is compiled from
 //     #include "smr_shader_dev.h"              the texel helpers of the built-in shaders, the same text
 //     #include "smr_user_shader_prelude.h"     PART 1: smr_shader_in, smr_plane, smr_affine, the accessors
-//     <the user's translation unit>            smr_fragment, optionally smr_vertex or smr_vertex_affine
+//     <the user's translation unit>            smr_fragment, optionally smr_vertex, smr_vertex_affine or smr_vertex_clip
 //     #define SMR_USER_SHADER_KERNEL
 //     #include "smr_user_shader_prelude.h"     PART 2: the kernel — k_shader_planes (smr_shaders.hip) with its two switches replaced by
 //                                              calls to the user's functions
@@ -48,6 +48,13 @@ struct smr_plane {
 //   X = xx * px + xy * py + cx,   Y = yx * px + yy * py + cy          (any parallelogram; no perspective)
 struct smr_affine {
     float xx, xy, yx, yy, cx, cy;
+};
+
+// clip vertex stage (SMR_HAS_VERTEX_CLIP): what smr_vertex_clip returns for one vertex of the quad — the homogeneous clip-space position
+// (x, y, z, w) and the tex_coords varying, interpolated perspective-correct over the quad's two triangles (include/smr.h)
+struct smr_clip_vertex {
+    float4 position;
+    float2 tex_coords;
 };
 
 // textureSample(textures[i], linear clamp-to-edge sampler, (u, v)): premultiplied RGBA in the target's blending space (linear light in
@@ -97,6 +104,9 @@ __device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv,
 #if defined(SMR_HAS_VERTEX) && defined(SMR_HAS_VERTEX_AFFINE)
 #error "a shader defines SMR_HAS_VERTEX or SMR_HAS_VERTEX_AFFINE, not both: one vertex stage per shader"
 #endif
+#if defined(SMR_HAS_VERTEX_CLIP) && (defined(SMR_HAS_VERTEX) || defined(SMR_HAS_VERTEX_AFFINE))
+#error "a shader defines SMR_HAS_VERTEX_CLIP or one of SMR_HAS_VERTEX and SMR_HAS_VERTEX_AFFINE, not both: one vertex stage per shader"
+#endif
 #ifdef SMR_HAS_VERTEX
 __device__ smr_plane smr_vertex(const smr_shader_in &in, int plane_id);
 #endif
@@ -104,6 +114,144 @@ __device__ smr_plane smr_vertex(const smr_shader_in &in, int plane_id);
 __device__ smr_affine smr_vertex_affine(const smr_shader_in &in, int plane_id);
 #endif
 
+#ifdef SMR_HAS_VERTEX_CLIP
+// ------------------------------------------------------------------------------------------------- the clip vertex stage and its rasteriser
+// The reference's vertex stage runs once per vertex of the quad of wgpu/common_pipeline/plane.rs:6-28 (four vertices, triangles 0 1 2 and
+// 2 3 0) and returns a vec4 clip position and the tex_coords varying.  Here it runs once per vertex per WORKGROUP: the 64 lanes of wave 0
+// call it (lane l: vertex l & 3 of plane first + (l >> 2) — 16 planes x 4 vertices), one lane per triangle turns the results into a record of
+// the table below, and after a barrier every lane reads the records (all lanes the same address: LDS broadcast reads).  Coverage is 2-D
+// homogeneous rasterisation (edge functions of (X, Y, 1) from cross products of the (x, y, w) vertices): no clipping step, no division
+// before coverage, a vertex behind the eye needs no special case.  include/smr.h states the contract and the order of the f32 operations.
+__device__ smr_clip_vertex smr_vertex_clip(const smr_shader_in &in, int plane_id, int vertex_index, float3 position, float2 tex_coords);
+
+// one triangle: 32 words, 16-byte aligned.  e[i] = (a, b, c) of the edge opposite vertex i; u, v, z, q = the planes (A, B, C) of
+// sum E_i * {u_i, v_i, z_i, w_i - z_i}: all affine in (X, Y); box = clip-space bounds of the triangle widened by one pixel (the whole range
+// when a vertex of the plane has w <= 0); flags bit i: edge i is inclusive, bit 3: drawn
+struct alignas(16) smr_clip_tri {
+    float e[3][3];
+    float u[3], v[3], z[3], q[3];
+    float box[4];  // x0, x1, y0, y1
+    unsigned int flags;
+    unsigned int pad[6];
+};
+static_assert(sizeof(smr_clip_tri) == 128, "a triangle record is 32 words");
+
+extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const UserShaderArgs a, const float *__restrict__ tables) {
+    __shared__ float s_vert[64][6];      // x, y, z, w, u, v of vertex (lane & 3) of plane slot (lane >> 2): 1 536 B
+    __shared__ smr_clip_tri s_tri[32];   // triangle (i & 1) of plane slot (i >> 1): 4 096 B
+    const float *dec = tables, *thr = tables + 256;
+    const int tid = (int)threadIdx.x;
+    const int x = blockIdx.x * 64 + (tid & 63), y = blockIdx.y * 4 + (tid >> 6);
+    const smr_shader_in in(a, dec);
+    const float W = (float)a.dst.w, H = (float)a.dst.h;
+    const int first = a.n_src == 0 ? -1 : 0, last = a.n_src == 0 ? -1 : a.n_src - 1;
+    // (no lane leaves before the second barrier: wave 0 of the last block column has lanes outside the target that own a vertex)
+    if (tid < 64) {
+        const int plane = first + (tid >> 2), k = tid & 3;
+        if (plane <= last) {
+            // plane.rs:11-28: (1, -1, 0) / (1, 1), (1, 1, 0) / (1, 0), (-1, 1, 0) / (0, 0), (-1, -1, 0) / (0, 1)
+            const float px = k < 2 ? 1.0f : -1.0f, py = (k == 1 || k == 2) ? 1.0f : -1.0f;
+            const smr_clip_vertex r = smr_vertex_clip(in, plane, k, make_float3(px, py, 0.0f), make_float2(k < 2 ? 1.0f : 0.0f, (k == 0 || k == 3) ? 1.0f : 0.0f));
+            float *o = s_vert[tid];
+            o[0] = r.position.x; o[1] = r.position.y; o[2] = r.position.z; o[3] = r.position.w;
+            o[4] = r.tex_coords.x; o[5] = r.tex_coords.y;
+        }
+    }
+    __syncthreads();
+    if (tid < 32) {
+        const int slot = tid >> 1, t = tid & 1;
+        if (first + slot <= last) {
+            // triangle t: vertices (0, 1, 2) or (2, 3, 0)
+            const float *P[3] = {s_vert[slot * 4 + 2 * t], s_vert[slot * 4 + 2 * t + 1], s_vert[slot * 4 + ((2 * t + 2) & 3)]};
+            smr_clip_tri T;
+            for (int i = 0; i < 3; i++) {
+                // (a, b, c)_i = p_j x p_k with p = (x, y, w).  The diagonal is p_2 x p_0 in triangle 0 and p_0 x p_2 in triangle 1: the same
+                // products with the subtraction's operands exchanged — exact negations of each other
+                const float *pj = P[(i + 1) % 3], *pk = P[(i + 2) % 3];
+                T.e[i][0] = pj[1] * pk[3] - pj[3] * pk[1];
+                T.e[i][1] = pj[3] * pk[0] - pj[0] * pk[3];
+                T.e[i][2] = pj[0] * pk[1] - pj[1] * pk[0];
+            }
+            const float D = (P[0][0] * T.e[0][0] + P[0][1] * T.e[0][1]) + P[0][3] * T.e[0][2];
+            for (int c = 0; c < 3; c++) {
+                T.u[c] = (T.e[0][c] * P[0][4] + T.e[1][c] * P[1][4]) + T.e[2][c] * P[2][4];
+                T.v[c] = (T.e[0][c] * P[0][5] + T.e[1][c] * P[1][5]) + T.e[2][c] * P[2][5];
+                T.z[c] = (T.e[0][c] * P[0][2] + T.e[1][c] * P[1][2]) + T.e[2][c] * P[2][2];
+                T.q[c] = (T.e[0][c] * (P[0][3] - P[0][2]) + T.e[1][c] * (P[1][3] - P[1][2])) + T.e[2][c] * (P[2][3] - P[2][2]);
+            }
+            // drawn: D > 0 and finite (front_face Ccw, cull_mode Back: wgpu/common_pipeline.rs:104-107; D <= 0 is a back face, an edge-on
+            // or degenerate plane, NaN a NaN in x, y or w) and every coefficient finite (an infinity or NaN in z, u, v; products that
+            // overflowed): such a triangle covers nothing
+            bool drawn = D > 0.0f && D <= 3.40282347e+38f;
+            for (int i = 0; i < 3; i++)
+                for (int c = 0; c < 3; c++) drawn = drawn && __builtin_fabsf(T.e[i][c]) <= 3.40282347e+38f;
+            for (int c = 0; c < 3; c++)
+                drawn = drawn && __builtin_fabsf(T.u[c]) <= 3.40282347e+38f && __builtin_fabsf(T.v[c]) <= 3.40282347e+38f &&
+                        __builtin_fabsf(T.z[c]) <= 3.40282347e+38f && __builtin_fabsf(T.q[c]) <= 3.40282347e+38f;
+            unsigned int flags = drawn ? 8u : 0u;
+            // top-left rule with clip-space Y pointing up: an edge owns the centres on it if a > 0, or a == 0 and b < 0
+            for (int i = 0; i < 3; i++)
+                if (T.e[i][0] > 0.0f || (T.e[i][0] == 0.0f && T.e[i][1] < 0.0f)) flags |= 1u << i;
+            T.flags = flags;
+            // With the plane's four w > 0 the triangle lies within the box of its vertices' x / w, y / w; widened by one pixel, which is far
+            // more than the divisions' rounding.  A NaN or infinite bound compares false below: no early-out on that side.
+            T.box[0] = T.box[2] = -3.40282347e+38f;
+            T.box[1] = T.box[3] = 3.40282347e+38f;
+            if (s_vert[slot * 4][3] > 0.0f && s_vert[slot * 4 + 1][3] > 0.0f && s_vert[slot * 4 + 2][3] > 0.0f && s_vert[slot * 4 + 3][3] > 0.0f) {
+                const float x0 = P[0][0] / P[0][3], x1 = P[1][0] / P[1][3], x2 = P[2][0] / P[2][3];
+                const float y0 = P[0][1] / P[0][3], y1 = P[1][1] / P[1][3], y2 = P[2][1] / P[2][3];
+                T.box[0] = fminf(fminf(x0, x1), x2) - 2.0f / W;
+                T.box[1] = fmaxf(fmaxf(x0, x1), x2) + 2.0f / W;
+                T.box[2] = fminf(fminf(y0, y1), y2) - 2.0f / H;
+                T.box[3] = fmaxf(fmaxf(y0, y1), y2) + 2.0f / H;
+            }
+            for (int i = 0; i < 6; i++) T.pad[i] = 0u;
+            s_tri[tid] = T;
+        }
+    }
+    __syncthreads();
+    if (x >= a.dst.w || y >= a.dst.h) return;
+    const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;          // @builtin(position).xy
+    const float X = fx / W * 2.0f - 1.0f, Y = 1.0f - fy / H * 2.0f;  // the pixel centre in clip space
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);                     // LoadOp::Clear(TRANSPARENT)
+    // the wave's 64 x 1 pixel span in clip space, from wave-uniform values (as in the affine stage's early-out below)
+    const int wx = blockIdx.x * 64, wy = blockIdx.y * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float wX0 = ((float)wx + 0.5f) / W * 2.0f - 1.0f, wX1 = ((float)(wx + 63) + 0.5f) / W * 2.0f - 1.0f;  // X is monotone in x
+    const float wY = 1.0f - ((float)wy + 0.5f) / H * 2.0f;                                                       // == Y of every lane
+    const int n_tri = min(2 * (last - first + 1), 2 * SMR_USER_SHADER_SOURCES);  // (the table's 32 records: smr_user_shader admits no more sources)
+    for (int i = 0; i < n_tri; i++) {  // plane first + (i >> 1), triangle i & 1: index order
+        const smr_clip_tri &T = s_tri[i];
+        // wave-uniform (every lane read the same words): scalar branches.  A wave none of whose pixels can be covered evaluates no edge
+        // function and no fragment code for this triangle.
+        const unsigned int flags = (unsigned int)__builtin_amdgcn_readfirstlane((int)T.flags);
+        if (!(flags & 8u)) continue;
+        const float bx0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(T.box[0])));
+        const float bx1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(T.box[1])));
+        const float by0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(T.box[2])));
+        const float by1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(T.box[3])));
+        if (wX1 < bx0 || wX0 > bx1 || wY < by0 || wY > by1) continue;
+        const float E0 = (T.e[0][0] * X + T.e[0][1] * Y) + T.e[0][2];
+        const float E1 = (T.e[1][0] * X + T.e[1][1] * Y) + T.e[1][2];
+        const float E2 = (T.e[2][0] * X + T.e[2][1] * Y) + T.e[2][2];
+        // covered: every E_i > 0, or == 0 on an inclusive edge (a NaN compares false)
+        if (!((E0 > 0.0f || (E0 == 0.0f && (flags & 1u))) && (E1 > 0.0f || (E1 == 0.0f && (flags & 2u))) && (E2 > 0.0f || (E2 == 0.0f && (flags & 4u)))))
+            continue;
+        // depth clip 0 <= z <= w, multiplied through by sum E > 0
+        const float Zn = (T.z[0] * X + T.z[1] * Y) + T.z[2], Qn = (T.q[0] * X + T.q[1] * Y) + T.q[2];
+        if (!(Zn >= 0.0f) || !(Qn >= 0.0f)) continue;
+        const float S = (E0 + E1) + E2;
+        if (!(S > 0.0f)) continue;  // (three concurrent edges through this centre: a triangle of no area that rounding let through)
+        const float u = ((T.u[0] * X + T.u[1] * Y) + T.u[2]) / S, v = ((T.v[0] * X + T.v[1] * Y) + T.v[2]) / S;
+        const float4 f = smr_fragment(in, first + (i >> 1), make_float2(u, v), make_float2(fx, fy));
+        const float k = 1.0f - f.w;  // PREMULTIPLIED_ALPHA_BLENDING (common_pipeline.rs:125)
+        float4 o = make_float4(f.x + acc.x * k, f.y + acc.y * k, f.z + acc.z * k, f.w + acc.w * k);
+        // render-target store, then what the next triangle's blend reads back
+        store_texel(a.dst, a.pxi, x, y, o, thr);
+        acc = load_texel(a.dst, a.pxi, x, y, dec);
+    }
+    if (acc.x == 0.f && acc.y == 0.f && acc.z == 0.f && acc.w == 0.f) *(u32 *)(a.dst.ptr + (size_t)y * a.dst.pitch + (size_t)x * 4) = 0u;
+}
+#else
 extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const UserShaderArgs a, const float *__restrict__ tables) {
     const float *dec = tables, *thr = tables + 256;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -171,5 +319,6 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
     }
     if (acc.x == 0.f && acc.y == 0.f && acc.z == 0.f && acc.w == 0.f) *(u32 *)(a.dst.ptr + (size_t)y * a.dst.pitch + (size_t)x * 4) = 0u;
 }
+#endif  // SMR_HAS_VERTEX_CLIP
 
 #endif  // SMR_USER_SHADER_KERNEL
