@@ -4,6 +4,8 @@
  * ratio kept (smr_dimensions); outside that plane the target shows eight bands whose colours are the texels of a palette strip (smr_load).
  * The third has a clip vertex stage (a homogeneous position and tex_coords per vertex of the quad): the same picture as a card turning
  * about its vertical axis by in.time radians, in perspective; once it has turned its back it is culled and only the bands show.
+ * The fourth is that card lit: its vertex stage also returns four varyings (SMR_VARYINGS) — a normal that turns with the card, interpolated
+ * perspective-correct, and a flat tint per triangle — and the fragment applies a diffuse factor.
  *   gcc -std=c11 -Iinclude examples/user_shader.c -o user_shader -Lsmelter_amd -l:libsmr_hip.so -Wl,-rpath,$PWD/smelter_amd -lm
  * Exit codes: 0 ok, 2 no HIP device (the shader was still compiled: that needs none), 1 anything else. */
 #include <stdio.h>
@@ -79,12 +81,58 @@ static const char *FLIP =
     "    return smr_load(in, plane_id, tx, ty);\n"
     "}\n";
 
+/* (tests/user_shader_sources_varyings.py carries the same text as LIT) */
+static const char *LIT =
+    "#define SMR_HAS_VERTEX_CLIP\n"
+    "#define SMR_VARYINGS 4\n"
+    "#define SMR_VARYINGS_FLAT 0x8\n"
+    "__device__ smr_clip_vertex_v<SMR_VARYINGS> smr_vertex_clip(const smr_shader_in &in, int plane_id, int vertex_index, float3 position, float2 tex_coords) {\n"
+    "    smr_clip_vertex_v<SMR_VARYINGS> o;\n"
+    "    o.position = make_float4(position.x, position.y, 0.0f, 1.0f);\n"
+    "    o.tex_coords = tex_coords;\n"
+    "    o.varyings[0] = 0.0f; o.varyings[1] = 0.0f; o.varyings[2] = -1.0f;  // the normal: towards the eye\n"
+    "    o.varyings[3] = 1.0f;\n"
+    "    if (plane_id != in.texture_count - 1) return o;\n"
+    "    const uint2 d = smr_dimensions(in, plane_id);\n"
+    "    const float W = (float)in.output_resolution.x, H = (float)in.output_resolution.y;\n"
+    "    const float fit = fminf(W / (float)d.x, H / (float)d.y) * 0.6f;\n"
+    "    const float sx = fit * (float)d.x / W, sy = fit * (float)d.y / H;  // the card's half extent in clip space\n"
+    "    const float c = cosf(in.time), s = sinf(in.time);\n"
+    "    const float xr = position.x * sx * c, zr = position.x * sx * s;\n"
+    "    const float w = 1.0f + zr / 2.5f;\n"
+    "    o.position = make_float4(xr, position.y * sy, 0.5f * w, w);\n"
+    "    const float nx = 0.5f * position.x, ny = 0.25f * position.y, nz = -1.0f;  // leaning outwards, then turned with the card\n"
+    "    o.varyings[0] = nx * c - nz * s; o.varyings[1] = ny; o.varyings[2] = nx * s + nz * c;\n"
+    "    o.varyings[3] = vertex_index == 0 ? 1.0f : 0.875f;  // the provoking vertex's value: triangle (0, 1, 2) full, (2, 3, 0) a shade darker\n"
+    "    return o;\n"
+    "}\n"
+    "__device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float4 position, const smr_varyings<SMR_VARYINGS> &v) {\n"
+    "    const uint2 d = smr_dimensions(in, plane_id);\n"
+    "    if (plane_id != in.texture_count - 1) {\n"
+    "        int band = (int)(uv.x * 8.0f);\n"
+    "        if (band > (int)d.x - 1) band = (int)d.x - 1;\n"
+    "        return smr_load(in, plane_id, band, 0);\n"
+    "    }\n"
+    "    int tx = (int)floorf(uv.x * (float)d.x), ty = (int)floorf(uv.y * (float)d.y);\n"
+    "    if (tx > (int)d.x - 1) tx = (int)d.x - 1;\n"
+    "    if (ty > (int)d.y - 1) ty = (int)d.y - 1;\n"
+    "    const float4 texel = smr_load(in, plane_id, tx, ty);\n"
+    "    const float len = sqrtf(v.v[0] * v.v[0] + v.v[1] * v.v[1] + v.v[2] * v.v[2]);\n"
+    "    const float diffuse = fmaxf((v.v[0] * -0.48f + v.v[1] * 0.6f + v.v[2] * -0.64f) / len, 0.0f);  // the light's direction is a unit vector\n"
+    "    const float k = (0.25f + 0.75f * diffuse) * v.v[3];\n"
+    "    return make_float4(texel.x * k, texel.y * k, texel.z * k, texel.w);\n"
+    "}\n";
+
 static const char *SCENE =
     "{\"type\":\"shader\",\"shader_id\":\"vignette\",\"resolution\":{\"width\":640,\"height\":360},"
     "\"shader_param\":{\"type\":\"f32\",\"value\":0.8},\"children\":[{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
 
 static const char *FLIP_SCENE =
     "{\"type\":\"shader\",\"shader_id\":\"flip\",\"resolution\":{\"width\":640,\"height\":360},"
+    "\"children\":[{\"type\":\"input_stream\",\"input_id\":\"palette\"},{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
+
+static const char *LIT_SCENE =
+    "{\"type\":\"shader\",\"shader_id\":\"lit\",\"resolution\":{\"width\":640,\"height\":360},"
     "\"children\":[{\"type\":\"input_stream\",\"input_id\":\"palette\"},{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
 
 static const char *SPIN_SCENE =
@@ -121,10 +169,21 @@ int main(void) {
         smr_shader_program_destroy(prog);
         return 1;
     }
+    smr_shader_program *lit = NULL;
+    rc = smr_shader_program_create(LIT, &lit);
+    if (rc != SMR_OK) {
+        fprintf(stderr, "the lit card shader did not compile (%d):\n%s\n", rc, lit ? smr_shader_program_log(lit) : "");
+        smr_shader_program_destroy(lit);
+        smr_shader_program_destroy(flip);
+        smr_shader_program_destroy(spin);
+        smr_shader_program_destroy(prog);
+        return 1;
+    }
 
     smr_ctx *ctx = NULL;
     if (smr_ctx_create(0, SMR_MODE_GPU_OPTIMIZED, SMR_DEFAULT_MAX_LAYOUTS, NULL, &ctx) != SMR_OK) {
         fprintf(stderr, "no HIP device\n");
+        smr_shader_program_destroy(lit);
         smr_shader_program_destroy(flip);
         smr_shader_program_destroy(spin);
         smr_shader_program_destroy(prog);
@@ -208,6 +267,22 @@ int main(void) {
         printf("card: corner %u %u %u, centre %u %u %u, launches %llu\n", corner[0], corner[1], corner[2], centre[0], centre[1], centre[2],
                (unsigned long long)launches);
         status = corner[0] == 255 && corner[1] == 0 && corner[2] == 0 && centre[1] > 0 && launches == 1 ? 0 : 1;
+
+        /* and with the lit card: the same coverage, the camera picture (200 throughout) darkened by the diffuse factor */
+        const unsigned unlit = centre[1];
+        if (status != 0 || smr_renderer_register_shader_program(r, "lit", lit) != 0 ||
+            smr_renderer_update_scene(r, "out", 640, 360, SMR_FRAME_RGBA, LIT_SCENE) != 0 ||
+            smr_renderer_render(r, 700000000, both, 2, out, 1, &n) != 0 || n != 1) {
+            if (status == 0) fprintf(stderr, "%s\n", smr_renderer_last_error(r));
+            status = 1;
+            free(got);
+            goto out;
+        }
+        smr_frame_download(out[0].ctx, out[0].frame, dst);
+        smr_shader_program_launches(lit, &launches);
+        printf("lit card: corner %u %u %u, centre %u %u %u, launches %llu\n", corner[0], corner[1], corner[2], centre[0], centre[1], centre[2],
+               (unsigned long long)launches);
+        status = corner[0] == 255 && corner[1] == 0 && corner[2] == 0 && centre[1] > 0 && centre[1] < unlit && launches == 1 ? 0 : 1;
         free(got);
     }
 out:
@@ -215,6 +290,7 @@ out:
     smr_frame_destroy(ctx, &cam);
     smr_frame_destroy(ctx, &palette);
     smr_ctx_destroy(ctx);
+    smr_shader_program_destroy(lit);
     smr_shader_program_destroy(flip);
     smr_shader_program_destroy(spin);
     smr_shader_program_destroy(prog); /* after the renderer it was registered in */

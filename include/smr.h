@@ -459,6 +459,9 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  *     __device__ smr_affine smr_vertex_affine(const smr_shader_in &in, int plane_id);
  *     // or, announced with `#define SMR_HAS_VERTEX_CLIP` instead (the clip vertex stage: below):
  *     __device__ smr_clip_vertex smr_vertex_clip(const smr_shader_in &in, int plane_id, int vertex_index, float3 position, float2 tex_coords);
+ *     // and, with `#define SMR_VARYINGS N` beside SMR_HAS_VERTEX_CLIP (varyings: below), these two instead of the first and the last:
+ *     __device__ smr_clip_vertex_v<SMR_VARYINGS> smr_vertex_clip(const smr_shader_in &in, int plane_id, int vertex_index, float3 position, float2 tex_coords);
+ *     __device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float4 position, const smr_varyings<SMR_VARYINGS> &v);
  * The node's semantics are those of the built-in kernels (the same kernel with the user's functions in place of the built-in switch):
  * the target is cleared to transparent, one plane per source is drawn in order (plane_id 0 .. texture_count - 1; one plane with
  * plane_id -1 when the node has no children), every plane blended premultiplied-alpha OVER and stored to the RGBA8 target before the
@@ -468,7 +471,7 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  * (cx, cy); a plane with sx <= 0 or sy <= 0 covers nothing.  smr_vertex_affine returns smr_affine {xx, xy, yx, yy, cx, cy}: corner
  * (px, py) of the unit quad, px, py in {-1, +1}, goes to clip space X = xx * px + xy * py + cx, Y = yx * px + yy * py + cy — a 2 x 2
  * matrix and a translation, so any parallelogram is expressible: rotated, sheared, scaled; perspective and per-vertex tex_coords need the
- * clip vertex stage below.  Still NOT expressible: varyings other than tex_coords, compute passes, raw surface access, WGSL text.  A pixel
+ * clip vertex stage below.  Still NOT expressible: compute passes, raw surface access, WGSL text.  A pixel
  * belongs to the plane when its centre, taken back into the quad (qx, qy) = M^-1 (X - cx, Y - cy) in f32, has -1 <= qx < 1 and
  * -1 < qy <= 1: a centre exactly on an edge belongs to the plane whose left / top edge (in quad space) it is; uv = ((qx + 1) / 2,
  * (1 - qy) / 2), position stays the pixel centre.  With xy == 0 and yx == 0 the plane IS smr_plane {xx, yy, cx, cy}, byte for byte,
@@ -483,8 +486,8 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  *   The clip vertex stage (SMR_HAS_VERTEX_CLIP) is the reference's: it is called once for each of the four vertices of every plane's quad
  * (smelter-render/src/wgpu/common_pipeline/plane.rs:6-28; vertex_index 0..3, `position` / `tex_coords` = (1, -1, 0) / (1, 1), (1, 1, 0) /
  * (1, 0), (-1, 1, 0) / (0, 0), (-1, -1, 0) / (0, 1)) and returns smr_clip_vertex {float4 position; float2 tex_coords;}: the homogeneous
- * clip-space position (x, y, z, w) and the one varying.  It may use what smr_fragment may use except smr_sample (WGSL has no textureSample
- * outside the fragment stage): smr_load, smr_dimensions, the parameters, in.*.  Any other varying is not expressible.  Defining it together
+ * clip-space position (x, y, z, w) and the tex_coords varying.  It may use what smr_fragment may use except smr_sample (WGSL has no textureSample
+ * outside the fragment stage): smr_load, smr_dimensions, the parameters, in.*.  Further varyings: SMR_VARYINGS, below.  Defining it together
  * with SMR_HAS_VERTEX or SMR_HAS_VERTEX_AFFINE is the same "#error" (one vertex stage per shader, SMR_ERR_INVALID, the message in the log).
  * smr_fragment keeps its signature: uv is the interpolated tex_coords, position the pixel centre.  The quad is drawn as the triangles
  * (0, 1, 2) then (2, 3, 0) by 2-D homogeneous rasterisation — no clipping step, no division before coverage.  With p_k = (x_k, y_k, w_k)
@@ -507,6 +510,26 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  *   covered by both triangles (possible only with contrived w: with w = 1 the second triangle of a folded quad is back-facing) is blended
  *   once per triangle in index order.  Everything after coverage is as for the other stages: premultiplied OVER, the store to the RGBA8
  *   target, the read back before the next triangle, the final transparent store.
+ *   Varyings.  A shader that defines SMR_HAS_VERTEX_CLIP may also `#define SMR_VARYINGS N`, 1 <= N <= 8: f32 varyings 0 .. N - 1, the
+ * reference's @location outputs.  smr_vertex_clip then returns smr_clip_vertex_v<SMR_VARYINGS> {float4 position; float2 tex_coords; float
+ * varyings[N];} and smr_fragment takes (in, plane_id, uv, float4 position, const smr_varyings<SMR_VARYINGS> &v) with v.v[k] varying k at the
+ * pixel and `position` the whole @builtin(position): (x + 0.5, y + 0.5, z / w, 1 / w).  Two optional bit masks choose each varying's
+ * interpolation: bit k of SMR_VARYINGS_FLAT makes varying k @interpolate(flat) — the value of the triangle's FIRST vertex (WebGPU's default
+ * provoking vertex: vertex 0 for triangle (0, 1, 2), vertex 2 for (2, 3, 0)); bit k of SMR_VARYINGS_LINEAR makes it @interpolate(linear),
+ * linear in screen space; neither bit: @interpolate(perspective), the rule of uv.  SMR_VARYINGS without SMR_HAS_VERTEX_CLIP, N outside
+ * 1 .. 8, a mask bit at or above N, or the same bit in both masks does not compile ("#error", SMR_ERR_INVALID, the message in the log).  A
+ * shader that does not define SMR_VARYINGS is compiled exactly as before.  In f32, every operation rounded on its own, with E_i, sum E and
+ * the depth sum Zn = sum E_i z_i as above and Wn = sum E_i w_i evaluated from its own plane ((a_0 w_0 + a_1 w_1) + a_2 w_2, likewise b, c):
+ *   - perspective: exactly as u, v — the plane A_t = (a_0 t_0 + a_1 t_1) + a_2 t_2, B_t, C_t likewise; per pixel ((A_t X + B_t Y) + C_t) / sum E.
+ *   - linear: the barycentrics in screen space are lambda_i = E_i w_i / sum E_j w_j; the plane is built from the products t_i * w_i, each
+ *     rounded first; per pixel ((A X + B Y) + C) / Wn.
+ *   - flat: the provoking vertex's 32-bit WORD, moved from the vertex stage's result to the fragment's argument as an integer: no arithmetic
+ *     touches it, so a NaN payload or an integer stored with __uint_as_float arrives bit for bit.
+ *   - position.z = Zn / Wn and position.w = sum E / Wn.  No pixel is dropped on account of Wn: where it is 0 (or where a vertex has
+ *     w <= 0 and it nearly cancels) these quotients and the linear varyings are what IEEE division gives — infinities or NaN.
+ *   A flat varying takes no part in the "every coefficient finite" rule of D above (a NaN there is data), and neither does Wn's plane; a
+ *   non-finite plane coefficient of a perspective or linear varying makes the triangle cover nothing, as for tex_coords — whether or not
+ *   the fragment reads that varying.  Declaring varyings changes neither coverage nor uv.
  * What a shader may use (the library puts it in front of the source):
  *     in.time (seconds, float)   in.output_resolution (uint2)   in.texture_count (int)          BaseShaderParameters (base_params.rs:7-12)
  *     float4 smr_sample(in, i, u, v)        source i through the linear clamp-to-edge sampler, decoded to the blending space;
@@ -703,7 +726,9 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      smr_renderer_add_shard, smr_renderer_input_ctx; user shaders (smr_shader_program_*, smr_user_shader,
  *      smr_renderer_register_shader_source / _program); in the user-shader language, no new C symbol: the affine vertex stage
  *      (smr_affine, smr_vertex_affine under SMR_HAS_VERTEX_AFFINE), smr_load and smr_dimensions; the clip vertex stage (smr_clip_vertex,
- *      smr_vertex_clip under SMR_HAS_VERTEX_CLIP: perspective and per-vertex tex_coords, drawn as two triangles).
+ *      smr_vertex_clip under SMR_HAS_VERTEX_CLIP: perspective and per-vertex tex_coords, drawn as two triangles); varyings (SMR_VARYINGS,
+ *      SMR_VARYINGS_FLAT, SMR_VARYINGS_LINEAR, smr_clip_vertex_v<N>, smr_varyings<N>, the float4 position): again no new C symbol —
+ *      UserShaderArgs, smr_user_shader, the renderer's registry and the bindings are unchanged.
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

@@ -2,7 +2,7 @@
 // A program is compiled from
 //     #include "smr_shader_dev.h"              the texel helpers of the built-in shaders, the same text
 //     #include "smr_user_shader_prelude.h"     PART 1: smr_shader_in, smr_plane, smr_affine, the accessors
-//     <the user's translation unit>            smr_fragment, optionally smr_vertex, smr_vertex_affine or smr_vertex_clip
+//     <the user's translation unit>            smr_fragment, optionally smr_vertex, smr_vertex_affine or smr_vertex_clip (with SMR_VARYINGS: varyings)
 //     #define SMR_USER_SHADER_KERNEL
 //     #include "smr_user_shader_prelude.h"     PART 2: the kernel — k_shader_planes (smr_shaders.hip) with its two switches replaced by
 //                                              calls to the user's functions
@@ -57,6 +57,19 @@ struct smr_clip_vertex {
     float2 tex_coords;
 };
 
+// varyings (SMR_VARYINGS N beside SMR_HAS_VERTEX_CLIP, 1 <= N <= 8: f32 varyings 0 .. N - 1; include/smr.h).  Part 1 is read before the user's text
+// and cannot see N: the carriers are templates, the user names them smr_clip_vertex_v<SMR_VARYINGS> and smr_varyings<SMR_VARYINGS>
+template <int N>
+struct smr_clip_vertex_v {
+    float4 position;
+    float2 tex_coords;
+    float varyings[N];
+};
+template <int N>
+struct smr_varyings {
+    float v[N];
+};
+
 // textureSample(textures[i], linear clamp-to-edge sampler, (u, v)): premultiplied RGBA in the target's blending space (linear light in
 // SMR_MODE_GPU_OPTIMIZED, the unorm values in SMR_MODE_CPU_OPTIMIZED); (0, 0, 0, 0) when i is out of range or the source is absent
 __device__ __forceinline__ float4 smr_sample(const smr_shader_in &in, int i, float u, float v) {
@@ -96,7 +109,7 @@ __device__ __forceinline__ float smr_smoothstep(float e0, float e1, float x) {
     return t * t * (3.0f - 2.0f * t);
 }
 
-// what the user's translation unit defines
+// what the user's translation unit defines (with SMR_VARYINGS it defines the overload that part 2 declares, and this one stays undefined)
 __device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float2 position);
 
 #else
@@ -106,6 +119,26 @@ __device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv,
 #endif
 #if defined(SMR_HAS_VERTEX_CLIP) && (defined(SMR_HAS_VERTEX) || defined(SMR_HAS_VERTEX_AFFINE))
 #error "a shader defines SMR_HAS_VERTEX_CLIP or one of SMR_HAS_VERTEX and SMR_HAS_VERTEX_AFFINE, not both: one vertex stage per shader"
+#endif
+#ifdef SMR_VARYINGS
+#ifndef SMR_HAS_VERTEX_CLIP
+#error "SMR_VARYINGS needs the clip vertex stage: only a shader that defines SMR_HAS_VERTEX_CLIP has per-vertex calls"
+#endif
+#if SMR_VARYINGS < 1 || SMR_VARYINGS > 8
+#error "SMR_VARYINGS is the number of f32 varyings, 1 to 8"
+#endif
+#ifndef SMR_VARYINGS_FLAT
+#define SMR_VARYINGS_FLAT 0
+#endif
+#ifndef SMR_VARYINGS_LINEAR
+#define SMR_VARYINGS_LINEAR 0
+#endif
+#if ((SMR_VARYINGS_FLAT) | (SMR_VARYINGS_LINEAR)) >> (SMR_VARYINGS)
+#error "SMR_VARYINGS_FLAT and SMR_VARYINGS_LINEAR have a bit per varying: bits at or above SMR_VARYINGS are not allowed"
+#endif
+#if (SMR_VARYINGS_FLAT) & (SMR_VARYINGS_LINEAR)
+#error "a varying is flat or linear, not both: SMR_VARYINGS_FLAT and SMR_VARYINGS_LINEAR share a bit"
+#endif
 #endif
 #ifdef SMR_HAS_VERTEX
 __device__ smr_plane smr_vertex(const smr_shader_in &in, int plane_id);
@@ -122,11 +155,32 @@ __device__ smr_affine smr_vertex_affine(const smr_shader_in &in, int plane_id);
 // the table below, and after a barrier every lane reads the records (all lanes the same address: LDS broadcast reads).  Coverage is 2-D
 // homogeneous rasterisation (edge functions of (X, Y, 1) from cross products of the (x, y, w) vertices): no clipping step, no division
 // before coverage, a vertex behind the eye needs no special case.  include/smr.h states the contract and the order of the f32 operations.
+#ifdef SMR_VARYINGS
+// with varyings the stages carry them: the vertex stage returns N more floats, the fragment gets them interpolated (flat, linear or
+// perspective by the two masks) and the whole @builtin(position) = (x + 0.5, y + 0.5, z / w, 1 / w)
+__device__ smr_clip_vertex_v<SMR_VARYINGS> smr_vertex_clip(const smr_shader_in &in, int plane_id, int vertex_index, float3 position, float2 tex_coords);
+__device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float4 position, const smr_varyings<SMR_VARYINGS> &v);
+#else
 __device__ smr_clip_vertex smr_vertex_clip(const smr_shader_in &in, int plane_id, int vertex_index, float3 position, float2 tex_coords);
+#endif
 
 // one triangle: 32 words, 16-byte aligned.  e[i] = (a, b, c) of the edge opposite vertex i; u, v, z, q = the planes (A, B, C) of
 // sum E_i * {u_i, v_i, z_i, w_i - z_i}: all affine in (X, Y); box = clip-space bounds of the triangle widened by one pixel (the whole range
 // when a vertex of the plane has w <= 0); flags bit i: edge i is inclusive, bit 3: drawn
+#ifdef SMR_VARYINGS
+// with N varyings the six pad words and what N needs beyond them: wn = the plane of Wn = sum E_i w_i (the divisor of linear varyings and of
+// position.z, position.w), vary[k] = the plane (A, B, C) of varying k — of sum E_i t_i (perspective), of sum E_i (t_i w_i) (linear) — or, for
+// a flat varying, the provoking vertex's word in vary[k][0].  29 + 3 N words, rounded up to 16 bytes: 32 words for N = 1, 56 for N = 8
+struct alignas(16) smr_clip_tri {
+    float e[3][3];
+    float u[3], v[3], z[3], q[3];
+    float box[4];  // x0, x1, y0, y1
+    unsigned int flags;
+    float wn[3];
+    unsigned int vary[SMR_VARYINGS][3];  // (words: a flat varying is moved, never computed with)
+};
+static_assert(sizeof(smr_clip_tri) == (29 + 3 * SMR_VARYINGS + 3) / 4 * 16 && sizeof(smr_clip_tri) <= 256, "a triangle record is at most 64 words");
+#else
 struct alignas(16) smr_clip_tri {
     float e[3][3];
     float u[3], v[3], z[3], q[3];
@@ -135,10 +189,16 @@ struct alignas(16) smr_clip_tri {
     unsigned int pad[6];
 };
 static_assert(sizeof(smr_clip_tri) == 128, "a triangle record is 32 words");
+#endif
 
 extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const UserShaderArgs a, const float *__restrict__ tables) {
+#ifdef SMR_VARYINGS
+    __shared__ float s_vert[64][6 + SMR_VARYINGS];  // x, y, z, w, u, v and the varyings of vertex (lane & 3) of plane slot (lane >> 2)
+    __shared__ smr_clip_tri s_tri[32];               // triangle (i & 1) of plane slot (i >> 1).  Both: 5 888 B for N = 1, 10 752 B for N = 8
+#else
     __shared__ float s_vert[64][6];      // x, y, z, w, u, v of vertex (lane & 3) of plane slot (lane >> 2): 1 536 B
     __shared__ smr_clip_tri s_tri[32];   // triangle (i & 1) of plane slot (i >> 1): 4 096 B
+#endif
     const float *dec = tables, *thr = tables + 256;
     const int tid = (int)threadIdx.x;
     const int x = blockIdx.x * 64 + (tid & 63), y = blockIdx.y * 4 + (tid >> 6);
@@ -151,10 +211,17 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
         if (plane <= last) {
             // plane.rs:11-28: (1, -1, 0) / (1, 1), (1, 1, 0) / (1, 0), (-1, 1, 0) / (0, 0), (-1, -1, 0) / (0, 1)
             const float px = k < 2 ? 1.0f : -1.0f, py = (k == 1 || k == 2) ? 1.0f : -1.0f;
+#ifdef SMR_VARYINGS
+            const smr_clip_vertex_v<SMR_VARYINGS> r = smr_vertex_clip(in, plane, k, make_float3(px, py, 0.0f), make_float2(k < 2 ? 1.0f : 0.0f, (k == 0 || k == 3) ? 1.0f : 0.0f));
+#else
             const smr_clip_vertex r = smr_vertex_clip(in, plane, k, make_float3(px, py, 0.0f), make_float2(k < 2 ? 1.0f : 0.0f, (k == 0 || k == 3) ? 1.0f : 0.0f));
+#endif
             float *o = s_vert[tid];
             o[0] = r.position.x; o[1] = r.position.y; o[2] = r.position.z; o[3] = r.position.w;
             o[4] = r.tex_coords.x; o[5] = r.tex_coords.y;
+#ifdef SMR_VARYINGS
+            for (int j = 0; j < SMR_VARYINGS; j++) o[6 + j] = r.varyings[j];  // (a copy: the word, whatever it holds)
+#endif
         }
     }
     __syncthreads();
@@ -188,6 +255,27 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
             for (int c = 0; c < 3; c++)
                 drawn = drawn && __builtin_fabsf(T.u[c]) <= 3.40282347e+38f && __builtin_fabsf(T.v[c]) <= 3.40282347e+38f &&
                         __builtin_fabsf(T.z[c]) <= 3.40282347e+38f && __builtin_fabsf(T.q[c]) <= 3.40282347e+38f;
+#ifdef SMR_VARYINGS
+            // Wn's plane is not part of `drawn`, and neither is a flat varying: a NaN there is data.  A perspective or linear varying's
+            // plane must be finite as u's and v's must.
+            for (int c = 0; c < 3; c++) T.wn[c] = (T.e[0][c] * P[0][3] + T.e[1][c] * P[1][3]) + T.e[2][c] * P[2][3];
+            for (int j = 0; j < SMR_VARYINGS; j++) {
+                if (((SMR_VARYINGS_FLAT) >> j) & 1) {
+                    // the provoking vertex is the triangle's first: vertex 0 of (0, 1, 2), vertex 2 of (2, 3, 0)
+                    T.vary[j][0] = (unsigned int)__float_as_int(P[0][6 + j]);
+                    T.vary[j][1] = T.vary[j][2] = 0u;
+                    continue;
+                }
+                const bool linear = ((SMR_VARYINGS_LINEAR) >> j) & 1;
+                const float t0 = linear ? P[0][6 + j] * P[0][3] : P[0][6 + j], t1 = linear ? P[1][6 + j] * P[1][3] : P[1][6 + j],
+                            t2 = linear ? P[2][6 + j] * P[2][3] : P[2][6 + j];
+                for (int c = 0; c < 3; c++) {
+                    const float coef = (T.e[0][c] * t0 + T.e[1][c] * t1) + T.e[2][c] * t2;
+                    drawn = drawn && __builtin_fabsf(coef) <= 3.40282347e+38f;
+                    T.vary[j][c] = (unsigned int)__float_as_int(coef);
+                }
+            }
+#endif
             unsigned int flags = drawn ? 8u : 0u;
             // top-left rule with clip-space Y pointing up: an edge owns the centres on it if a > 0, or a == 0 and b < 0
             for (int i = 0; i < 3; i++)
@@ -205,7 +293,9 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
                 T.box[2] = fminf(fminf(y0, y1), y2) - 2.0f / H;
                 T.box[3] = fmaxf(fmaxf(y0, y1), y2) + 2.0f / H;
             }
+#ifndef SMR_VARYINGS
             for (int i = 0; i < 6; i++) T.pad[i] = 0u;
+#endif
             s_tri[tid] = T;
         }
     }
@@ -242,7 +332,24 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
         const float S = (E0 + E1) + E2;
         if (!(S > 0.0f)) continue;  // (three concurrent edges through this centre: a triangle of no area that rounding let through)
         const float u = ((T.u[0] * X + T.u[1] * Y) + T.u[2]) / S, v = ((T.v[0] * X + T.v[1] * Y) + T.v[2]) / S;
+#ifdef SMR_VARYINGS
+        // Wn = sum E_i w_i: lambda_i = E_i w_i / Wn are the barycentrics in screen space.  No pixel is dropped on its account: where it is 0
+        // the quotients below are what IEEE division gives
+        const float Wn = (T.wn[0] * X + T.wn[1] * Y) + T.wn[2];
+        smr_varyings<SMR_VARYINGS> vy;
+#pragma unroll
+        for (int j = 0; j < SMR_VARYINGS; j++) {
+            if (((SMR_VARYINGS_FLAT) >> j) & 1) {
+                vy.v[j] = __int_as_float((int)T.vary[j][0]);
+            } else {
+                const float n = (__int_as_float((int)T.vary[j][0]) * X + __int_as_float((int)T.vary[j][1]) * Y) + __int_as_float((int)T.vary[j][2]);
+                vy.v[j] = n / ((((SMR_VARYINGS_LINEAR) >> j) & 1) ? Wn : S);
+            }
+        }
+        const float4 f = smr_fragment(in, first + (i >> 1), make_float2(u, v), make_float4(fx, fy, Zn / Wn, S / Wn), vy);
+#else
         const float4 f = smr_fragment(in, first + (i >> 1), make_float2(u, v), make_float2(fx, fy));
+#endif
         const float k = 1.0f - f.w;  // PREMULTIPLIED_ALPHA_BLENDING (common_pipeline.rs:125)
         float4 o = make_float4(f.x + acc.x * k, f.y + acc.y * k, f.z + acc.z * k, f.w + acc.w * k);
         // render-target store, then what the next triangle's blend reads back
