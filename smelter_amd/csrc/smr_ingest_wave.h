@@ -442,8 +442,18 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
     const int klo[2] = {hm.z & 0xff, hm.w & 0xff}, khi[2] = {(hm.z >> 8) & 0xff, (hm.w >> 8) & 0xff};  // (0xff / 0xff: no such tile)
     const int tx0 = (J.single ? 16 : 32) * pair;
     const int d_w = J.dst.w, d_h = J.dst.h;
-    u8 *const d_ptr = J.dst.ptr;
-    const u32 d_pitch = J.dst.pitch;
+    u8 *d_ptr = J.dst.ptr;
+    u32 d_pitch = J.dst.pitch;
+    // What the tile-row path needs from the job record stays in scalar registers for the whole piece.  Left to itself the compiler re-reads a
+    // field where it is used: per tile row a scalar load of `v_meta` and, four instructions later, a wait for it that also drains every LDS
+    // gather in flight (scalar loads and LDS share a counter).
+    const int2 *v_meta = J.v_meta;
+    const uint4 *v_frag = J.v_frag;
+    SMR_KEEP_SCALAR(v_meta);
+    SMR_KEEP_SCALAR(v_frag);
+    SMR_KEEP_SCALAR(d_ptr);
+    SMR_KEEP_SCALAR(d_pitch);
+    // (a pointer kept this way is no longer known to point into device memory: every access through these goes by g_ld_* / g_st_*)
 
     // ---- staging: loads of the next chunk's raw footprint into registers, landed in LDS after the chunk at hand is converted
     const int ys = w_ys(NKS), cs = w_cs(NKS);
@@ -483,7 +493,7 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
     const u32 c_colb = nv ? 2u * (u32)c_col0c : (u32)c_col0c;
     auto issue = [&](int c) {
         if (RG || FX) return;  // (rg_load, block by block; fx_issue)
-        if (SMR_WAVE_ABL & 256) c = J.v_meta[vt0].x;  // profiling: always the same rows (cache hits)
+        if (SMR_WAVE_ABL & 256) c = g_ld_uniform_i32x2(v_meta + vt0).x;  // profiling: always the same rows (cache hits)
         if (SMR_WAVE_ABL & 128) {                       // profiling: no global loads
 #pragma unroll
             for (int k = 0; k < NYL; k++) py[k] = 0x80808080u + (u32)c;
@@ -687,7 +697,6 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
         for (int c = 0; c < NCH; c++) ring[i][c] = (ring_t)(0u);
     auto ring_quad = [&](int i, int ch, int p) { return make_uint4(ring[i][ch][4 * p], ring[i][ch][4 * p + 1], ring[i][ch][4 * p + 2], ring[i][ch][4 * p + 3]); };
     uint4 bvh[KV_N], bvl[KV_N];
-    const uint4 *const v_frag = J.v_frag;
     const bool dj = DIRECT && Dg != nullptr && J.layer >= 0;  // (uniform)
     const int d_ox = J.ox, d_oy = J.oy, d_layer = J.layer;
     u32 cls_next[2] = {0xffu, 0xffu};
@@ -695,8 +704,8 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
 #pragma unroll
         for (int p = 0; p < KV_N; p++)
             if (p < KV) {
-                bvh[p] = v_frag[(((size_t)t * KV + p) * 2) * 64 + lane];
-                bvl[p] = v_frag[(((size_t)t * KV + p) * 2 + 1) * 64 + lane];
+                bvh[p] = g_ld_u32x4(v_frag + (((size_t)t * KV + p) * 2) * 64 + lane);
+                bvl[p] = g_ld_u32x4(v_frag + (((size_t)t * KV + p) * 2 + 1) * 64 + lane);
             }
         if (dj) {  // direct output: the class of the 128x16 output tile this lane's four pixels of tile row t fall into
 #pragma unroll
@@ -739,27 +748,40 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
     constexpr bool DEFER = (RG || FX) && !DIRECT && !SA && NKS_T != 0 && (SMR_WAVE_DEFER_STORES != 0);  // (the generic builds sit at the register limit: immediate stores there)
     u32 pend_px[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
     int pend_vt = -1;  // (uniform) the tile row waiting to be stored, -1 = none
+    // A lane's four finished pixels of tile i of tile row vt_s: columns x .. x + 3 of output row y.  Whether the whole 16 x 16 tile lies inside the
+    // destination is decided once, for the wave (every operand is uniform): an interior tile — all of them when the tile's size is a multiple of 16,
+    // all but the last row and column otherwise — is one address and ONE 16-byte store per lane, straight-line.  As a per-lane choice between the
+    // 16-byte store and the ragged tail the compiler merged the two (a 12-byte store and a 4-byte one at + 12 under three levels of exec masks): twice
+    // the store instructions, each counted by the in-order memory counter the chunk loop waits on.
+    auto store_px4 = [&](int vt_s, int i, const u32 (&q)[4]) {
+        const int y = 16 * vt_s + l16, x = tx0 + 16 * i + 4 * lq;
+        const bool keep = !(SMR_WAVE_ABL & 16) || q[0] == 0x12345678u;  // (16: profiling, all work but no store traffic)
+        u8 *op = d_ptr + dev_mad24((u32)y, d_pitch, (u32)x * 4u);  // (a tile is far below 4 GiB)
+        if (16 * vt_s + 15 < d_h && tx0 + 16 * i + 15 < d_w) {  // (uniform) an interior tile
+            if (keep) g_st_u32x4(op, make_uint4(q[0], q[1], q[2], q[3]));
+            return;
+        }
+        if (y < d_h && x < d_w && keep) {  // an edge tile: per lane
+            if (x + 3 < d_w) {
+                g_st_u32x4(op, make_uint4(q[0], q[1], q[2], q[3]));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (x + k < d_w) g_st_u32(op + 4 * k, q[k]);
+            }
+        }
+    };
     auto store_rows = [&](int vt_s, const u32 (&p)[2][4]) {
 #pragma unroll
         for (int i = 0; i < W_NTI; i++) {
             if (klo[i] == 0xff) continue;
-            const int y = 16 * vt_s + l16, x = tx0 + 16 * i + 4 * lq;  // lane holds columns x .. x + 3 of output row y
-            if (y < d_h && x < d_w && (!(SMR_WAVE_ABL & 16) || p[i][0] == 0x12345678u)) {  // (16: profiling, all work but no store traffic)
-                u8 *op = d_ptr + dev_mad24((u32)y, d_pitch, (u32)x * 4u);  // (a tile is far below 4 GiB)
-                if (x + 3 < d_w) {
-                    *(uint4 *)op = make_uint4(p[i][0], p[i][1], p[i][2], p[i][3]);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        if (x + k < d_w) ((u32 *)op)[k] = p[i][k];
-                }
-            }
+            store_px4(vt_s, i, p[i]);
         }
     };
     int vt = vt0;
-    int2 vm = J.v_meta[vt0];
-    int2 vm_next = J.v_meta[min(vt0 + 1, vt1)];  // (read a tile ahead: a scalar load the loop never waits for)
-    const int c_first = vm.x, c_last = J.v_meta[vt1].y;
+    int2 vm = g_ld_uniform_i32x2(v_meta + vt0);
+    int2 vm_next = g_ld_uniform_i32x2(v_meta + min(vt0 + 1, vt1));  // (read a tile ahead: a scalar load the loop never waits for)
+    const int c_first = vm.x, c_last = g_ld_uniform_i32x2(v_meta + vt1).y;
     if (!SA) fetch_bv(vt0);
     if (RG) {
 #pragma unroll
@@ -964,12 +986,12 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
                     const int y = 16 * c - 1 + 4 * lq + k - perp;
                     const u32 px = AL ? (w_encode_px(acc[i][0][k], acc[i][1][k], acc[i][2][k], s_thr) & 0xffffffu) | (unorm8(acc[i][AL ? 3 : 0][k]) << 24)
                                       : w_encode_px(acc[i][0][k], acc[i][1][k], acc[i][2][k], s_thr);
-                    if (y >= y_lo && y <= y_hi && x < d_w) *(u32 *)(d_ptr + dev_mad24((u32)y, d_pitch, (u32)x * 4u)) = px;
+                    if (y >= y_lo && y <= y_hi && x < d_w) g_st_u32(d_ptr + dev_mad24((u32)y, d_pitch, (u32)x * 4u), px);
                 }
             }
             while (vt <= vt1 && vm.y == c) {
                 vt++;
-                if (vt <= vt1) { vm = vm_next; vm_next = J.v_meta[min(vt + 1, vt1)]; }
+                if (vt <= vt1) { vm = vm_next; vm_next = g_ld_uniform_i32x2(v_meta + min(vt + 1, vt1)); }
             }
             if (c + 1 < c_last) issue(c + 2);
             continue;
@@ -1018,6 +1040,10 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
             // 33.8 us: the kernel's floor is its memory traffic, profiles/r04_wave_ablation.txt — and kept for the earlier weight request.)
             f32x4 o[2][4];
             u32 px[2][4];
+            // (the chunk range of the tile row after the next: a scalar load, first looked at a tile row later — wherever in this tile row the compiler
+            //  issues it, nothing waits for it at once.  While it is outstanding the encode's LDS gathers are waited for batch by batch with lgkmcnt(0):
+            //  scalar loads return out of order and share the gathers' counter.  Settling it behind pass 2 was measured neutral and is not done.)
+            const int2 vm_ahead = g_ld_uniform_i32x2(v_meta + min(vt + 2, vt1));
 #pragma unroll
             for (int i = 0; i < W_NTI; i++) {
 #pragma unroll
@@ -1042,7 +1068,7 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
             vt++;
             if (vt <= vt1) {
                 vm = vm_next;
-                vm_next = J.v_meta[min(vt + 1, vt1)];
+                vm_next = vm_ahead;
                 if (!(SMR_WAVE_ABL & 512)) fetch_bv(vt);  // (512: profiling, every tile with the first tile's weights)
             }
 #pragma unroll
@@ -1094,14 +1120,19 @@ __device__ __forceinline__ void wave_piece(const WJob &J, const MDirect *__restr
 #endif
                     if (direct && (!(SMR_DIRECT_ABL & 2) || yq == 0x12345678u)) m_direct_store(Dg, d_ox + x, d_oy + y, odd, yq, mine, other);  // (2: profiling, no direct stores)
                 }
+                if (!DIRECT) {  // (the interior / edge split of the deferred stores)
+                    store_px4(vt_now, i, px[i]);
+                    continue;
+                }
+                // (direct output: the choice between the Y'CbCr store and the RGBA8 one is per lane)
                 if (!direct && y < d_h && x < d_w && (!(SMR_WAVE_ABL & 16) || px[i][0] == 0x12345678u)) {  // (16: profiling, all work but no store traffic)
                     u8 *op = d_ptr + dev_mad24((u32)y, d_pitch, (u32)x * 4u);  // (a tile is far below 4 GiB)
                     if (x + 3 < d_w) {
-                        *(uint4 *)op = make_uint4(px[i][0], px[i][1], px[i][2], px[i][3]);
+                        g_st_u32x4(op, make_uint4(px[i][0], px[i][1], px[i][2], px[i][3]));
                     } else {
 #pragma unroll
                         for (int k = 0; k < 4; k++)
-                            if (x + k < d_w) ((u32 *)op)[k] = px[i][k];
+                            if (x + k < d_w) g_st_u32(op + 4 * k, px[i][k]);
                     }
                 }
             }

@@ -78,6 +78,13 @@ __device__ __forceinline__ uint4 g_ld_u32x4(const void *p) { const g_u32x4 v = *
 __device__ __forceinline__ void g_st_u32(void *p, u32 v) { *SMR_GLOBAL_PTR(u32, p) = v; }
 __device__ __forceinline__ void g_st_u32x3(void *p, u32 a, u32 b, u32 c) { g_u32x3 v; v.x = a; v.y = b; v.z = c; *SMR_GLOBAL_PTR(g_u32x3, p) = v; }
 __device__ __forceinline__ void g_st_u32x4(void *p, uint4 q) { g_u32x4 v; v.x = q.x; v.y = q.y; v.z = q.z; v.w = q.w; *SMR_GLOBAL_PTR(g_u32x4, p) = v; }
+// A wave-uniform record of a table no kernel writes while this one runs (weight band metadata): read through the constant address space, i.e. by
+// a scalar load into scalar registers — a load from a pointer that was itself loaded is otherwise a vector load, one copy per lane.
+typedef int g_i32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int2 g_ld_uniform_i32x2(const void *p) { const g_i32x2 v = *((__attribute__((address_space(4))) const g_i32x2 *)(uintptr_t)(p)); return make_int2(v.x, v.y); }
+// A wave-uniform value stays in the scalar registers it is in: the compiler otherwise re-reads a kernel-argument field wherever it is used
+// (a scalar load and a wait for it inside a loop) instead of keeping it.
+#define SMR_KEEP_SCALAR(x) asm volatile("" : "+s"(x))
 #else  // (host code and the lane emulator: plain accesses)
 static inline u32 g_ld_u32(const void *p) { return *(const u32 *)p; }
 static inline uint2 g_ld_u32x2(const void *p) { return *(const uint2 *)p; }
@@ -85,6 +92,8 @@ static inline uint4 g_ld_u32x4(const void *p) { return *(const uint4 *)p; }
 static inline void g_st_u32(void *p, u32 v) { *(u32 *)p = v; }
 static inline void g_st_u32x3(void *p, u32 a, u32 b, u32 c) { ((u32 *)p)[0] = a; ((u32 *)p)[1] = b; ((u32 *)p)[2] = c; }
 static inline void g_st_u32x4(void *p, uint4 q) { *(uint4 *)p = q; }
+static inline int2 g_ld_uniform_i32x2(const void *p) { return *(const int2 *)p; }
+#define SMR_KEEP_SCALAR(x) do { } while (0)
 #endif
 
 // one pinned-host + device staging slot of the per-call layout parameter ring

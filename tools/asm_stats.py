@@ -8,7 +8,7 @@ from collections import Counter
 
 def kernels(path):
     txt = open(path).read()
-    for m in re.finditer(r'^(\S+):\s*; @\1\n(.*?)\n\s*s_endpgm', txt, re.S | re.M):
+    for m in re.finditer(r'^(\S+):\s*; @\1\n(.*?)\n\.Lfunc_end', txt, re.S | re.M):  # (the whole body: an early exit's s_endpgm may sit in the middle)
         yield m.group(1), m.group(2)
 
 def mix(body):
