@@ -6,6 +6,8 @@
  * about its vertical axis by in.time radians, in perspective; once it has turned its back it is culled and only the bands show.
  * The fourth is that card lit: its vertex stage also returns four varyings (SMR_VARYINGS) — a normal that turns with the card, interpolated
  * perspective-correct, and a flat tint per triangle — and the fragment applies a diffuse factor.
+ * The fifth uses screen-space derivatives (SMR_DERIVATIVES): the camera picture through a disc whose edge is anti-aliased over exactly one
+ * pixel at any resolution — the distance to the edge measured in units of smr_fwidth of that distance.
  *   gcc -std=c11 -Iinclude examples/user_shader.c -o user_shader -Lsmelter_amd -l:libsmr_hip.so -Wl,-rpath,$PWD/smelter_amd -lm
  * Exit codes: 0 ok, 2 no HIP device (the shader was still compiled: that needs none), 1 anything else. */
 #include <stdio.h>
@@ -123,6 +125,23 @@ static const char *LIT =
     "    return make_float4(texel.x * k, texel.y * k, texel.z * k, texel.w);\n"
     "}\n";
 
+/* (tests/user_shader_sources_derivatives.py carries the same text as DISC) */
+static const char *DISC =
+    "#define SMR_DERIVATIVES\n"
+    "__device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float2 position) {\n"
+    "    const float W = (float)in.output_resolution.x, H = (float)in.output_resolution.y;\n"
+    "    const float dx = position.x - (0.5f * W + 0.3f), dy = position.y - (0.5f * H + 0.1f);\n"
+    "    const float d = sqrtf(dx * dx + dy * dy);\n"
+    "    const float footprint = smr_fwidth(d);  // (before any branch: a derivative wants the whole quad)\n"
+    "    const float cover = fminf(fmaxf(0.5f - (d - 0.4f * fminf(W, H)) / footprint, 0.0f), 1.0f);\n"
+    "    const uint2 s = smr_dimensions(in, plane_id);\n"
+    "    int tx = (int)floorf(uv.x * (float)s.x), ty = (int)floorf(uv.y * (float)s.y);\n"
+    "    if (tx > (int)s.x - 1) tx = (int)s.x - 1;\n"
+    "    if (ty > (int)s.y - 1) ty = (int)s.y - 1;\n"
+    "    const float4 t = smr_load(in, plane_id, tx, ty);\n"
+    "    return make_float4(t.x * cover, t.y * cover, t.z * cover, t.w * cover);\n"
+    "}\n";
+
 static const char *SCENE =
     "{\"type\":\"shader\",\"shader_id\":\"vignette\",\"resolution\":{\"width\":640,\"height\":360},"
     "\"shader_param\":{\"type\":\"f32\",\"value\":0.8},\"children\":[{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
@@ -134,6 +153,10 @@ static const char *FLIP_SCENE =
 static const char *LIT_SCENE =
     "{\"type\":\"shader\",\"shader_id\":\"lit\",\"resolution\":{\"width\":640,\"height\":360},"
     "\"children\":[{\"type\":\"input_stream\",\"input_id\":\"palette\"},{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
+
+static const char *DISC_SCENE =
+    "{\"type\":\"shader\",\"shader_id\":\"disc\",\"resolution\":{\"width\":640,\"height\":360},"
+    "\"children\":[{\"type\":\"input_stream\",\"input_id\":\"cam\"}]}";
 
 static const char *SPIN_SCENE =
     "{\"type\":\"shader\",\"shader_id\":\"rotate\",\"resolution\":{\"width\":640,\"height\":360},"
@@ -179,10 +202,22 @@ int main(void) {
         smr_shader_program_destroy(prog);
         return 1;
     }
+    smr_shader_program *disc = NULL;
+    rc = smr_shader_program_create(DISC, &disc);
+    if (rc != SMR_OK) {
+        fprintf(stderr, "the disc shader did not compile (%d):\n%s\n", rc, disc ? smr_shader_program_log(disc) : "");
+        smr_shader_program_destroy(disc);
+        smr_shader_program_destroy(lit);
+        smr_shader_program_destroy(flip);
+        smr_shader_program_destroy(spin);
+        smr_shader_program_destroy(prog);
+        return 1;
+    }
 
     smr_ctx *ctx = NULL;
     if (smr_ctx_create(0, SMR_MODE_GPU_OPTIMIZED, SMR_DEFAULT_MAX_LAYOUTS, NULL, &ctx) != SMR_OK) {
         fprintf(stderr, "no HIP device\n");
+        smr_shader_program_destroy(disc);
         smr_shader_program_destroy(lit);
         smr_shader_program_destroy(flip);
         smr_shader_program_destroy(spin);
@@ -283,6 +318,22 @@ int main(void) {
         printf("lit card: corner %u %u %u, centre %u %u %u, launches %llu\n", corner[0], corner[1], corner[2], centre[0], centre[1], centre[2],
                (unsigned long long)launches);
         status = corner[0] == 255 && corner[1] == 0 && corner[2] == 0 && centre[1] > 0 && centre[1] < unlit && launches == 1 ? 0 : 1;
+
+        /* the camera picture alone through the anti-aliased disc: transparent in the corner, the picture (alpha 200) in the centre, and on
+         * the disc's rightmost pixel (the centre is at 320.3, the radius 144) a coverage strictly between the two */
+        if (status != 0 || smr_renderer_register_shader_program(r, "disc", disc) != 0 ||
+            smr_renderer_update_scene(r, "out", 640, 360, SMR_FRAME_RGBA, DISC_SCENE) != 0 ||
+            smr_renderer_render(r, 700000000, both, 1, out, 1, &n) != 0 || n != 1) {
+            if (status == 0) fprintf(stderr, "%s\n", smr_renderer_last_error(r));
+            status = 1;
+            free(got);
+            goto out;
+        }
+        smr_frame_download(out[0].ctx, out[0].frame, dst);
+        smr_shader_program_launches(disc, &launches);
+        const uint8_t *rim = got + (180 * 640 + 464) * 4;
+        printf("disc: corner alpha %u, centre %u alpha %u, rim alpha %u, launches %llu\n", corner[3], centre[0], centre[3], rim[3], (unsigned long long)launches);
+        status = corner[3] == 0 && centre[3] == 200 && rim[3] > 0 && rim[3] < centre[3] && launches == 1 ? 0 : 1;
         free(got);
     }
 out:
@@ -290,6 +341,7 @@ out:
     smr_frame_destroy(ctx, &cam);
     smr_frame_destroy(ctx, &palette);
     smr_ctx_destroy(ctx);
+    smr_shader_program_destroy(disc);
     smr_shader_program_destroy(lit);
     smr_shader_program_destroy(flip);
     smr_shader_program_destroy(spin);

@@ -471,7 +471,8 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  * (cx, cy); a plane with sx <= 0 or sy <= 0 covers nothing.  smr_vertex_affine returns smr_affine {xx, xy, yx, yy, cx, cy}: corner
  * (px, py) of the unit quad, px, py in {-1, +1}, goes to clip space X = xx * px + xy * py + cx, Y = yx * px + yy * py + cy — a 2 x 2
  * matrix and a translation, so any parallelogram is expressible: rotated, sheared, scaled; perspective and per-vertex tex_coords need the
- * clip vertex stage below.  Still NOT expressible: compute passes, raw surface access, WGSL text.  A pixel
+ * clip vertex stage below; screen-space derivatives (dpdx, dpdy, fwidth): SMR_DERIVATIVES, below.  Still NOT expressible: compute passes,
+ * raw surface access, discard, WGSL text.  A pixel
  * belongs to the plane when its centre, taken back into the quad (qx, qy) = M^-1 (X - cx, Y - cy) in f32, has -1 <= qx < 1 and
  * -1 < qy <= 1: a centre exactly on an edge belongs to the plane whose left / top edge (in quad space) it is; uv = ((qx + 1) / 2,
  * (1 - qy) / 2), position stays the pixel centre.  With xy == 0 and yx == 0 the plane IS smr_plane {xx, yy, cx, cy}, byte for byte,
@@ -530,6 +531,34 @@ SMR_API int smr_builtin_shader(smr_ctx *ctx, uint32_t id, const void *params, si
  *   A flat varying takes no part in the "every coefficient finite" rule of D above (a NaN there is data), and neither does Wn's plane; a
  *   non-finite plane coefficient of a perspective or linear varying makes the triangle cover nothing, as for tex_coords — whether or not
  *   the fragment reads that varying.  Declaring varyings changes neither coverage nor uv.
+ *   Derivatives.  A shader that puts `#define SMR_DERIVATIVES` at the top of its source — alone or beside any vertex stage, with or without
+ * SMR_VARYINGS — may call, from smr_fragment only, WGSL's dpdx, dpdy, fwidth and their Fine / Coarse forms:
+ *     float smr_dpdx(float v)          smr_dpdy(float v)          smr_fwidth(float v)
+ *     float smr_dpdx_fine(float v)     smr_dpdy_fine(float v)     smr_fwidth_fine(float v)
+ *     float smr_dpdx_coarse(float v)   smr_dpdy_coarse(float v)   smr_fwidth_coarse(float v)        and float2 overloads of all nine, per component
+ * The target is dealt out in 2 x 2 pixel QUADS aligned to even target coordinates: a = (x0, y0), b = (x0 + 1, y0), c = (x0, y0 + 1),
+ * d = (x0 + 1, y0 + 1).  Window y grows downwards: dpdy(position.y) == +1.
+ *   - coarse: for all four pixels dpdx = v_b - v_a and dpdy = v_c - v_a.
+ *   - fine: dpdx is the pixel's own row's right value minus its left one (v_b - v_a for a and b, v_d - v_c for c and d), dpdy its own
+ *     column's lower value minus its upper one (v_c - v_a for a and c, v_d - v_b for b and d).
+ *   - plain: smr_dpdx, smr_dpdy and smr_fwidth ARE the coarse ones.  WGSL leaves the choice to the implementation; this is a definition of
+ *     this library, not a measurement of any other.
+ *   - fwidth = |dpdx| + |dpdy| of the same flavour.  Each derivative is one f32 subtraction, rounded once; fwidth two fabs and one add.
+ *   Helper invocations.  For every plane (every triangle, in the clip stage) smr_fragment runs for all four pixels of a quad if at least
+ * one of them is covered — covered by the rules above, unchanged (coverage, depth clip, sum E > 0).  A pixel of that quad that is not
+ * covered is a HELPER, and so is a pixel outside the target when its width or height is odd.  A helper gets the same plane_id; its uv,
+ * position, varyings and position.z / w come from the same formulas in the same operation order at its own pixel centre, with no coverage test
+ * applied: extrapolated values — in the clip stage sum E may be <= 0 there and the quotients are what IEEE division gives.  A helper's
+ * return value is dropped: it never stores to the target and never loads from it; smr_sample clamps and smr_load bounds-checks as always, so
+ * a helper cannot touch memory outside the sources either.  Coverage, uv, blend and the picture of a shader that calls no derivative are
+ * unchanged by the macro, byte for byte.
+ *   Uniformity.  As in WGSL a derivative must be called in control flow that is uniform across the quad (all four invocations reach the call, or
+ * none: before any branch on a per-pixel value; a branch on plane_id, the parameters or in.* is uniform).  Elsewhere its value is
+ * unspecified — it is only ever a register value, never an address: an invocation that is not there reads as 0.  Calling a derivative from
+ * a vertex stage is not diagnosed; its value there is unspecified.  Calling any of the nine without SMR_DERIVATIVES does not compile
+ * (a static_assert whose message names SMR_DERIVATIVES; SMR_ERR_INVALID, the message in smr_shader_program_log).  A shader that does not
+ * define SMR_DERIVATIVES is compiled exactly as before.  With it the launch is the same (64 x 4 pixels per 256-thread workgroup); inside, a
+ * wave covers 32 x 2 pixels as sixteen quads of four consecutive lanes, and a neighbour's value is one register move.
  * What a shader may use (the library puts it in front of the source):
  *     in.time (seconds, float)   in.output_resolution (uint2)   in.texture_count (int)          BaseShaderParameters (base_params.rs:7-12)
  *     float4 smr_sample(in, i, u, v)        source i through the linear clamp-to-edge sampler, decoded to the blending space;
@@ -727,8 +756,9 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      smr_renderer_register_shader_source / _program); in the user-shader language, no new C symbol: the affine vertex stage
  *      (smr_affine, smr_vertex_affine under SMR_HAS_VERTEX_AFFINE), smr_load and smr_dimensions; the clip vertex stage (smr_clip_vertex,
  *      smr_vertex_clip under SMR_HAS_VERTEX_CLIP: perspective and per-vertex tex_coords, drawn as two triangles); varyings (SMR_VARYINGS,
- *      SMR_VARYINGS_FLAT, SMR_VARYINGS_LINEAR, smr_clip_vertex_v<N>, smr_varyings<N>, the float4 position): again no new C symbol —
- *      UserShaderArgs, smr_user_shader, the renderer's registry and the bindings are unchanged.
+ *      SMR_VARYINGS_FLAT, SMR_VARYINGS_LINEAR, smr_clip_vertex_v<N>, smr_varyings<N>, the float4 position); screen-space derivatives
+ *      (SMR_DERIVATIVES: smr_dpdx, smr_dpdy, smr_fwidth and their _fine / _coarse forms, on 2 x 2 pixel quads with helper invocations):
+ *      again no new C symbol — UserShaderArgs, smr_user_shader and its launch, the renderer's registry and the bindings are unchanged.
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

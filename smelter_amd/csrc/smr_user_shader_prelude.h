@@ -109,6 +109,20 @@ __device__ __forceinline__ float smr_smoothstep(float e0, float e1, float x) {
     return t * t * (3.0f - 2.0f * t);
 }
 
+// screen-space derivatives on 2 x 2 pixel quads (a shader that puts `#define SMR_DERIVATIVES` at its top; include/smr.h): WGSL's dpdx, dpdy,
+// fwidth and their Fine / Coarse forms, of a float or, component by component, a float2.  Callable from smr_fragment only.  Part 1 is read
+// before the user's text and cannot see the macro: the eighteen functions are templates with a defaulted parameter (a call names none),
+// declared here and defined in part 2 — with the macro by quad exchanges, without it by a static_assert that names the macro.
+template <typename T>
+struct smr_derivatives_enabled { static constexpr bool value = false; };
+#define SMR_DERIVATIVE_DECLARE(name)                                  \
+    template <typename T = void> __device__ __forceinline__ float name(float v); \
+    template <typename T = void> __device__ __forceinline__ float2 name(float2 v);
+SMR_DERIVATIVE_DECLARE(smr_dpdx) SMR_DERIVATIVE_DECLARE(smr_dpdy) SMR_DERIVATIVE_DECLARE(smr_fwidth)
+SMR_DERIVATIVE_DECLARE(smr_dpdx_fine) SMR_DERIVATIVE_DECLARE(smr_dpdy_fine) SMR_DERIVATIVE_DECLARE(smr_fwidth_fine)
+SMR_DERIVATIVE_DECLARE(smr_dpdx_coarse) SMR_DERIVATIVE_DECLARE(smr_dpdy_coarse) SMR_DERIVATIVE_DECLARE(smr_fwidth_coarse)
+#undef SMR_DERIVATIVE_DECLARE
+
 // what the user's translation unit defines (with SMR_VARYINGS it defines the overload that part 2 declares, and this one stays undefined)
 __device__ float4 smr_fragment(const smr_shader_in &in, int plane_id, float2 uv, float2 position);
 
@@ -146,6 +160,64 @@ __device__ smr_plane smr_vertex(const smr_shader_in &in, int plane_id);
 #ifdef SMR_HAS_VERTEX_AFFINE
 __device__ smr_affine smr_vertex_affine(const smr_shader_in &in, int plane_id);
 #endif
+
+#ifdef SMR_DERIVATIVES
+// ------------------------------------------------------------------------------------------------- derivatives: quad mode
+// With SMR_DERIVATIVES the 64 x 4 pixels of a workgroup are dealt out in 2 x 2 quads, aligned to even target coordinates: wave w covers the
+// 32 x 2 block at (32 (w & 1), 2 (w >> 1)), lane l is pixel (2 (l >> 2) + (l & 1), (l >> 1) & 1) of it — four consecutive lanes are the quad
+//     a = (x0, y0)   b = (x0 + 1, y0)   c = (x0, y0 + 1)   d = (x0 + 1, y0 + 1)          lanes 0, 1, 2, 3 of the quad
+// which is what v_mov_b32_dpp quad_perm permutes: a neighbour's value is one register move away, no LDS, no ds_bpermute.  No lane leaves for
+// being outside the target or outside a plane: per plane (per triangle) the fragment function runs on all four lanes of every quad with a
+// covered pixel — the others are HELPERS, whose inputs are the same formulas at their own pixel centres, whose result is dropped, and
+// which neither store to the target nor load from it.  row_mask = bank_mask = 0xf; bound_ctrl: a disabled lane reads as 0 (a derivative
+// called where the quad's control flow has diverged is unspecified — and only ever a value, never an address).
+#ifdef SMR_EMU
+#define SMR_QUAD_PERM(x, ctrl) dev_mov_dpp_quad_perm((x), (ctrl))  // (the lane emulator's: tests/emu/emu_user_shader_quad.cpp)
+#else
+#define SMR_QUAD_PERM(x, ctrl) __builtin_amdgcn_mov_dpp((x), (ctrl), 0xf, 0xf, true)
+#endif
+// quad_perm control c: lane k of the quad reads lane (c >> 2 k) & 3.  0x00 / 0x55 / 0xAA: lanes 0 / 1 / 2 for all four
+template <int CTRL>
+__device__ __forceinline__ float smr_quad_read(float v) {
+    return __int_as_float(SMR_QUAD_PERM(__float_as_int(v), CTRL));
+}
+// does any pixel of the quad hold `c`?  Two exchanges: with the horizontal neighbour [1, 0, 3, 2], then with the other row [2, 3, 0, 1].  Called
+// with all of the wave's lanes active
+__device__ __forceinline__ bool smr_quad_any(bool c) {
+    int m = c ? 1 : 0;
+    m |= SMR_QUAD_PERM(m, 0xB1);
+    m |= SMR_QUAD_PERM(m, 0x4E);
+    return m != 0;
+}
+// Each derivative is ONE f32 subtraction.  Coarse: b - a and c - a for all four pixels.  Fine: the pixel's own row's right minus left
+// ([1, 1, 3, 3] - [0, 0, 2, 2]), its own column's lower minus upper ([2, 3, 2, 3] - [0, 1, 0, 1]).  Window y grows downwards.  The plain forms are
+// the coarse ones (a definition: include/smr.h).  fwidth = |dpdx| + |dpdy| of the same flavour.
+template <typename T> __device__ __forceinline__ float smr_dpdx_coarse(float v) { return smr_quad_read<0x55>(v) - smr_quad_read<0x00>(v); }
+template <typename T> __device__ __forceinline__ float smr_dpdy_coarse(float v) { return smr_quad_read<0xAA>(v) - smr_quad_read<0x00>(v); }
+template <typename T> __device__ __forceinline__ float smr_dpdx_fine(float v) { return smr_quad_read<0xF5>(v) - smr_quad_read<0xA0>(v); }
+template <typename T> __device__ __forceinline__ float smr_dpdy_fine(float v) { return smr_quad_read<0xEE>(v) - smr_quad_read<0x44>(v); }
+template <typename T> __device__ __forceinline__ float smr_dpdx(float v) { return smr_dpdx_coarse<T>(v); }
+template <typename T> __device__ __forceinline__ float smr_dpdy(float v) { return smr_dpdy_coarse<T>(v); }
+template <typename T> __device__ __forceinline__ float smr_fwidth_coarse(float v) { return __builtin_fabsf(smr_dpdx_coarse<T>(v)) + __builtin_fabsf(smr_dpdy_coarse<T>(v)); }
+template <typename T> __device__ __forceinline__ float smr_fwidth_fine(float v) { return __builtin_fabsf(smr_dpdx_fine<T>(v)) + __builtin_fabsf(smr_dpdy_fine<T>(v)); }
+template <typename T> __device__ __forceinline__ float smr_fwidth(float v) { return smr_fwidth_coarse<T>(v); }
+#define SMR_DERIVATIVE_DEFINE(name) \
+    template <typename T> __device__ __forceinline__ float2 name(float2 v) { return make_float2(name<T>(v.x), name<T>(v.y)); }
+#else
+#define SMR_DERIVATIVE_DEFINE(name)                                                                                                              \
+    template <typename T> __device__ __forceinline__ float name(float) {                                                                         \
+        static_assert(smr_derivatives_enabled<T>::value, #name ": derivatives need `#define SMR_DERIVATIVES` at the top of the shader source"); \
+        return 0.0f;                                                                                                                             \
+    }                                                                                                                                            \
+    template <typename T> __device__ __forceinline__ float2 name(float2) {                                                                       \
+        static_assert(smr_derivatives_enabled<T>::value, #name ": derivatives need `#define SMR_DERIVATIVES` at the top of the shader source"); \
+        return make_float2(0.0f, 0.0f);                                                                                                          \
+    }
+#endif
+SMR_DERIVATIVE_DEFINE(smr_dpdx) SMR_DERIVATIVE_DEFINE(smr_dpdy) SMR_DERIVATIVE_DEFINE(smr_fwidth)
+SMR_DERIVATIVE_DEFINE(smr_dpdx_fine) SMR_DERIVATIVE_DEFINE(smr_dpdy_fine) SMR_DERIVATIVE_DEFINE(smr_fwidth_fine)
+SMR_DERIVATIVE_DEFINE(smr_dpdx_coarse) SMR_DERIVATIVE_DEFINE(smr_dpdy_coarse) SMR_DERIVATIVE_DEFINE(smr_fwidth_coarse)
+#undef SMR_DERIVATIVE_DEFINE
 
 #ifdef SMR_HAS_VERTEX_CLIP
 // ------------------------------------------------------------------------------------------------- the clip vertex stage and its rasteriser
@@ -201,7 +273,12 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
 #endif
     const float *dec = tables, *thr = tables + 256;
     const int tid = (int)threadIdx.x;
+#ifdef SMR_DERIVATIVES
+    // quad mode: the lane-to-pixel map above.  The vertex stage and the table below do not depend on it
+    const int x = blockIdx.x * 64 + 32 * ((tid >> 6) & 1) + 2 * ((tid & 63) >> 2) + (tid & 1), y = blockIdx.y * 4 + 2 * (tid >> 7) + ((tid >> 1) & 1);
+#else
     const int x = blockIdx.x * 64 + (tid & 63), y = blockIdx.y * 4 + (tid >> 6);
+#endif
     const smr_shader_in in(a, dec);
     const float W = (float)a.dst.w, H = (float)a.dst.h;
     const int first = a.n_src == 0 ? -1 : 0, last = a.n_src == 0 ? -1 : a.n_src - 1;
@@ -300,14 +377,26 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
         }
     }
     __syncthreads();
+#ifdef SMR_DERIVATIVES
+    const bool in_target = x < a.dst.w && y < a.dst.h;  // (a lane outside an odd target lives on as a helper: it never touches the target)
+#else
     if (x >= a.dst.w || y >= a.dst.h) return;
+#endif
     const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;          // @builtin(position).xy
     const float X = fx / W * 2.0f - 1.0f, Y = 1.0f - fy / H * 2.0f;  // the pixel centre in clip space
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);                     // LoadOp::Clear(TRANSPARENT)
+#ifdef SMR_DERIVATIVES
+    // the wave's 32 x 2 pixel block in clip space, from wave-uniform values: its two end columns' X, its two rows' Y (wY0 the upper, > wY1)
+    const int wv = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wx = blockIdx.x * 64 + 32 * (wv & 1), wy = blockIdx.y * 4 + 2 * (wv >> 1);
+    const float wX0 = ((float)wx + 0.5f) / W * 2.0f - 1.0f, wX1 = ((float)(wx + 31) + 0.5f) / W * 2.0f - 1.0f;  // X is monotone in x
+    const float wY0 = 1.0f - ((float)wy + 0.5f) / H * 2.0f, wY1 = 1.0f - ((float)(wy + 1) + 0.5f) / H * 2.0f;    // Y is monotone in y
+#else
     // the wave's 64 x 1 pixel span in clip space, from wave-uniform values (as in the affine stage's early-out below)
     const int wx = blockIdx.x * 64, wy = blockIdx.y * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const float wX0 = ((float)wx + 0.5f) / W * 2.0f - 1.0f, wX1 = ((float)(wx + 63) + 0.5f) / W * 2.0f - 1.0f;  // X is monotone in x
     const float wY = 1.0f - ((float)wy + 0.5f) / H * 2.0f;                                                       // == Y of every lane
+#endif
     const int n_tri = min(2 * (last - first + 1), 2 * SMR_USER_SHADER_SOURCES);  // (the table's 32 records: smr_user_shader admits no more sources)
     for (int i = 0; i < n_tri; i++) {  // plane first + (i >> 1), triangle i & 1: index order
         const smr_clip_tri &T = s_tri[i];
@@ -319,10 +408,23 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
         const float bx1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(T.box[1])));
         const float by0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(T.box[2])));
         const float by1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(T.box[3])));
+#ifdef SMR_DERIVATIVES
+        if (wX1 < bx0 || wX0 > bx1 || wY0 < by0 || wY1 > by1) continue;  // (the box is a pixel wider than the triangle: a quad that straddles it keeps its helpers)
+#else
         if (wX1 < bx0 || wX0 > bx1 || wY < by0 || wY > by1) continue;
+#endif
         const float E0 = (T.e[0][0] * X + T.e[0][1] * Y) + T.e[0][2];
         const float E1 = (T.e[1][0] * X + T.e[1][1] * Y) + T.e[1][2];
         const float E2 = (T.e[2][0] * X + T.e[2][1] * Y) + T.e[2][2];
+#ifdef SMR_DERIVATIVES
+        // the same three rules, as a value: every lane of the wave is still here, the quad's four answers are combined, and a quad with a
+        // covered pixel goes on whole — its other pixels as helpers, with this triangle's planes extrapolated to their centres
+        const float Zn = (T.z[0] * X + T.z[1] * Y) + T.z[2], Qn = (T.q[0] * X + T.q[1] * Y) + T.q[2];
+        const float S = (E0 + E1) + E2;
+        const bool covered = in_target && (E0 > 0.0f || (E0 == 0.0f && (flags & 1u))) && (E1 > 0.0f || (E1 == 0.0f && (flags & 2u))) &&
+                             (E2 > 0.0f || (E2 == 0.0f && (flags & 4u))) && Zn >= 0.0f && Qn >= 0.0f && S > 0.0f;
+        if (!smr_quad_any(covered)) continue;
+#else
         // covered: every E_i > 0, or == 0 on an inclusive edge (a NaN compares false)
         if (!((E0 > 0.0f || (E0 == 0.0f && (flags & 1u))) && (E1 > 0.0f || (E1 == 0.0f && (flags & 2u))) && (E2 > 0.0f || (E2 == 0.0f && (flags & 4u)))))
             continue;
@@ -331,6 +433,7 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
         if (!(Zn >= 0.0f) || !(Qn >= 0.0f)) continue;
         const float S = (E0 + E1) + E2;
         if (!(S > 0.0f)) continue;  // (three concurrent edges through this centre: a triangle of no area that rounding let through)
+#endif
         const float u = ((T.u[0] * X + T.u[1] * Y) + T.u[2]) / S, v = ((T.v[0] * X + T.v[1] * Y) + T.v[2]) / S;
 #ifdef SMR_VARYINGS
         // Wn = sum E_i w_i: lambda_i = E_i w_i / Wn are the barycentrics in screen space.  No pixel is dropped on its account: where it is 0
@@ -350,26 +453,46 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
 #else
         const float4 f = smr_fragment(in, first + (i >> 1), make_float2(u, v), make_float2(fx, fy));
 #endif
+#ifdef SMR_DERIVATIVES
+        if (!covered) continue;  // a helper's result is dropped
+#endif
         const float k = 1.0f - f.w;  // PREMULTIPLIED_ALPHA_BLENDING (common_pipeline.rs:125)
         float4 o = make_float4(f.x + acc.x * k, f.y + acc.y * k, f.z + acc.z * k, f.w + acc.w * k);
         // render-target store, then what the next triangle's blend reads back
         store_texel(a.dst, a.pxi, x, y, o, thr);
         acc = load_texel(a.dst, a.pxi, x, y, dec);
     }
+#ifdef SMR_DERIVATIVES
+    if (!in_target) return;
+#endif
     if (acc.x == 0.f && acc.y == 0.f && acc.z == 0.f && acc.w == 0.f) *(u32 *)(a.dst.ptr + (size_t)y * a.dst.pitch + (size_t)x * 4) = 0u;
 }
 #else
 extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const UserShaderArgs a, const float *__restrict__ tables) {
     const float *dec = tables, *thr = tables + 256;
+#ifdef SMR_DERIVATIVES
+    // quad mode (above): wave w covers the 32 x 2 block at (32 (w & 1), 2 (w >> 1)), four consecutive lanes a 2 x 2 quad; no lane leaves
+    const int tid = (int)threadIdx.x;
+    const int x = blockIdx.x * 64 + 32 * ((tid >> 6) & 1) + 2 * ((tid & 63) >> 2) + (tid & 1), y = blockIdx.y * 4 + 2 * (tid >> 7) + ((tid >> 1) & 1);
+    const bool in_target = x < a.dst.w && y < a.dst.h;  // (a lane outside an odd target lives on as a helper: it never touches the target)
+#else
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= a.dst.w || y >= a.dst.h) return;
+#endif
     const smr_shader_in in(a, dec);
     const float W = (float)a.dst.w, H = (float)a.dst.h;
     const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;          // @builtin(position).xy
     const float X = fx / W * 2.0f - 1.0f, Y = 1.0f - fy / H * 2.0f;  // the pixel centre in clip space
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);                     // LoadOp::Clear(TRANSPARENT)
     const int first = a.n_src == 0 ? -1 : 0, last = a.n_src == 0 ? -1 : a.n_src - 1;
-#ifdef SMR_HAS_VERTEX_AFFINE
+#if defined(SMR_HAS_VERTEX_AFFINE) && defined(SMR_DERIVATIVES)
+    // the wave's 32 x 2 pixel block in clip space, from wave-uniform values only: its two end columns' X, its two rows' Y (wY0 the upper, > wY1)
+    const int wv = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wx = blockIdx.x * 64 + 32 * (wv & 1), wy = blockIdx.y * 4 + 2 * (wv >> 1);
+    const float wX0 = ((float)wx + 0.5f) / W * 2.0f - 1.0f, wX1 = ((float)(wx + 31) + 0.5f) / W * 2.0f - 1.0f;  // X is monotone in x
+    const float wY0 = 1.0f - ((float)wy + 0.5f) / H * 2.0f, wY1 = 1.0f - ((float)(wy + 1) + 0.5f) / H * 2.0f;    // Y is monotone in y
+    const float px_w = 2.0f / W, px_h = 2.0f / H;  // one pixel in clip space
+#elif defined(SMR_HAS_VERTEX_AFFINE)
     // The wave's 64 x 1 pixel span in clip space, from wave-uniform values only (the row of a wave is threadIdx.x >> 6 of any of its
     // lanes): with smr_vertex_affine's result — a function of the kernel arguments and the plane — the early-out below is a scalar branch.
     const int wx = blockIdx.x * 64, wy = blockIdx.y * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -399,8 +522,13 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
             // a near-singular sliver (entries near 1 with det near 1e-4: about a tenth of a pixel wide at 1920, edges uncertain by
             // about one) the two tests may disagree on the sliver's few pixels.  A NaN compares false: no early-out, the exact test decides.
             const float ex = __builtin_fabsf(m.xx) + __builtin_fabsf(m.xy) + px_w, ey = __builtin_fabsf(m.yx) + __builtin_fabsf(m.yy) + px_h;
+#ifdef SMR_DERIVATIVES
+            // (the block's dy lie between its two rows'; the box is a pixel wider than the plane: a quad that straddles it keeps its helpers)
+            if (wX1 - m.cx < -ex || wX0 - m.cx > ex || wY0 - m.cy < -ey || wY1 - m.cy > ey) continue;
+#else
             const float wdy = wY - m.cy;
             if (wX1 - m.cx < -ex || wX0 - m.cx > ex || wdy < -ey || wdy > ey) continue;
+#endif
             const float dx = X - m.cx, dy = Y - m.cy;
             qx = (dx * m.yy - dy * m.xy) / det;
             qy = (dy * m.xx - dx * m.yx) / det;
@@ -415,15 +543,28 @@ extern "C" __global__ __launch_bounds__(256) void smr_user_shader_kernel(const U
         const float qx = (X - cx) / sx, qy = (Y - cy) / sy;  // position within the unit quad [-1, 1]^2
 #endif
         // coverage: pixel centre inside the quad; a centre exactly on an edge belongs to the quad whose left / top edge it is
+#ifdef SMR_DERIVATIVES
+        // the same rule, as a value: every lane of the wave is still here (the `continue`s above are the plane's, the same for all of them),
+        // and a quad with a covered pixel goes on whole — its other pixels as helpers, uv from the same formulas at their own centres
+        const bool covered = in_target && qx >= -1.0f && qx < 1.0f && qy > -1.0f && qy <= 1.0f;
+        if (!smr_quad_any(covered)) continue;
+#else
         if (!(qx >= -1.0f && qx < 1.0f && qy > -1.0f && qy <= 1.0f)) continue;
+#endif
         const float u = (qx + 1.0f) * 0.5f, v = (1.0f - qy) * 0.5f;  // plane.rs:11-28: (1, -1) <-> tex (1, 1)
         const float4 f = smr_fragment(in, plane, make_float2(u, v), make_float2(fx, fy));
+#ifdef SMR_DERIVATIVES
+        if (!covered) continue;  // a helper's result is dropped
+#endif
         const float k = 1.0f - f.w;  // PREMULTIPLIED_ALPHA_BLENDING (common_pipeline.rs:125)
         float4 o = make_float4(f.x + acc.x * k, f.y + acc.y * k, f.z + acc.z * k, f.w + acc.w * k);
         // render-target store, then what the next plane's blend reads back
         store_texel(a.dst, a.pxi, x, y, o, thr);
         acc = load_texel(a.dst, a.pxi, x, y, dec);
     }
+#ifdef SMR_DERIVATIVES
+    if (!in_target) return;
+#endif
     if (acc.x == 0.f && acc.y == 0.f && acc.z == 0.f && acc.w == 0.f) *(u32 *)(a.dst.ptr + (size_t)y * a.dst.pitch + (size_t)x * 4) = 0u;
 }
 #endif  // SMR_HAS_VERTEX_CLIP
