@@ -654,6 +654,17 @@ SMR_API int smr_scene_node_children(const smr_scene *scene, int node, int32_t *o
 SMR_API int smr_scene_node_layouts(smr_scene *scene, int node, int64_t pts_ns, const uint32_t *child_wh, uint32_t n_children,
                                    uint32_t mode, smr_layout *out, uint32_t cap, uint32_t *n_out, uint32_t *out_width,
                                    uint32_t *out_height);
+/* Host only. ImageRenderParams::start_pts of node `node` (an Image node, else SMR_ERR_INVALID): the pts its animation clock counts from.
+ * An Image component with an `id` keeps it across smr_scene_update while the previous scene holds an Image of the same id, image_id, width
+ * and height (scene/image_component.rs:91-120); otherwise, and for every component without an id, it is the pts of the last render before the
+ * update (smr_scene_node_layouts' clock; 0 before any render).  Static images carry it too, as in the reference. */
+SMR_API int smr_scene_node_start_pts(const smr_scene *scene, int node, int64_t *start_pts_ns);
+/* Host only. AnimatedAsset::render's choice (animated_image.rs:127-136) in exact integers.  With pts_0 = 0, pts_k = delays_ns[0] + .. +
+ * delays_ns[k - 1] and D = the sum of all delays (1 if that is 0: the reference's 1 ns rule): t = max(pts_ns - start_pts_ns, 0) mod D (the
+ * reference would underflow on a negative difference; the clamp is this library's definition), and the result is the k that minimises
+ * |pts_k - t|, the FIRST such k on a tie (Rust's min_by_key).  No wrap-around: near the end of the loop the last frame shows, not frame 0.
+ * < 0 on null / n_frames == 0. */
+SMR_API int smr_animated_frame_index(const uint64_t *delays_ns, uint32_t n_frames, int64_t pts_ns, int64_t start_pts_ns);
 /* scene/transition/{cubic_bezier,bounce}.rs and smelter-api/src/video/color.rs, exported for the parity tests */
 SMR_API double smr_cubic_bezier_easing(double progress, double x1, double y1, double x2, double y2);
 SMR_API double smr_bounce_easing(double progress);
@@ -663,7 +674,8 @@ SMR_API int smr_parse_color(const char *text, uint8_t rgba[4]);
  * `Renderer` of smelter-render/src/state.rs:96-252 over the scene engine and the kernels above:
  *   Renderer::new              -> smr_renderer_create (stream_fallback_timeout: state.rs:43-52, render_loop.rs:29)
  *   register_input / unregister_input / unregister_output (state.rs:102-121)
- *   register_renderer(Image)   -> smr_renderer_register_image (bitmap pixels; decoding is the caller's)
+ *   register_renderer(Image)   -> smr_renderer_register_image (bitmap pixels; decoding is the caller's),
+ *                                 smr_renderer_register_animated_image (the decoded frames of a GIF and their delays)
  *   register_renderer(Shader)  -> smr_renderer_register_shader (a built-in kernel id), smr_renderer_register_shader_source /
  *                                 _program (a user shader written in HIP C++; WGSL text is out of scope)
  *   update_scene               -> smr_renderer_update_scene(output_id, resolution, OutputFrameFormat, scene JSON) (state.rs:177-189)
@@ -692,6 +704,20 @@ SMR_API const char *smr_renderer_last_error(const smr_renderer *r);
 SMR_API int smr_renderer_register_input(smr_renderer *r, const char *input_id);
 SMR_API int smr_renderer_unregister_input(smr_renderer *r, const char *input_id);
 SMR_API int smr_renderer_register_image(smr_renderer *r, const char *image_id, const uint8_t *rgba_straight, uint32_t width, uint32_t height);
+/* AnimatedAsset::new (transformations/image/animated_image.rs:41-118): n_frames straight-alpha RGBA8 frames of width x height, tightly
+ * packed one after the other, and their delays.  Every frame is premultiplied once, here, and kept on the renderer's own context; an Image
+ * node of this asset shows, at every render, frame smr_animated_frame_index(delays_ns, n_frames, pts, the node's start_pts) — at its own size
+ * the frame itself, at another size the frame drawn into the node's resolution by the image pass.  SMR_ERR_INVALID: n_frames == 0 ("Animated
+ * image does not contain any frames."), n_frames > 1000 ("Detected over 1000 frames inside the animated image. This case is not currently
+ * supported."), a delay sum above INT64_MAX, and whatever smr_renderer_register_image refuses (null arguments, a zero size, an id that
+ * names a static or animated image already).  n_frames == 1 registers exactly what smr_renderer_register_image would (the reference's
+ * SingleFrame fallback; the delay is ignored).  A failed allocation is SMR_ERR_OOM and registers nothing. */
+SMR_API int smr_renderer_register_animated_image(smr_renderer *r, const char *image_id, const uint8_t *rgba_straight_frames,
+                                                 uint32_t width, uint32_t height, uint32_t n_frames, const uint64_t *delays_ns);
+/* Launches of the image pass so far, all lanes (which path drew the Image nodes is observable without a kernel counter slot).  The image
+ * pass runs once per output and render, before the graph walk: every Image node whose size differs from its asset's is drawn into the
+ * node's resolution — animated assets at every render, static ones once per node surface — by ONE launch per 16 such nodes. */
+SMR_API int smr_renderer_image_launches(const smr_renderer *r, uint64_t *count);
 SMR_API int smr_renderer_register_shader(smr_renderer *r, const char *shader_id, uint32_t builtin_id);
 /* A user shader ("user shaders" above) under `shader_id`; registering an id again replaces what it named (built-in or not).
  * _source compiles (blocking, host only) and the renderer owns the program; a source that does not compile fails with the status of
@@ -758,7 +784,9 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      smr_vertex_clip under SMR_HAS_VERTEX_CLIP: perspective and per-vertex tex_coords, drawn as two triangles); varyings (SMR_VARYINGS,
  *      SMR_VARYINGS_FLAT, SMR_VARYINGS_LINEAR, smr_clip_vertex_v<N>, smr_varyings<N>, the float4 position); screen-space derivatives
  *      (SMR_DERIVATIVES: smr_dpdx, smr_dpdy, smr_fwidth and their _fine / _coarse forms, on 2 x 2 pixel quads with helper invocations):
- *      again no new C symbol — UserShaderArgs, smr_user_shader and its launch, the renderer's registry and the bindings are unchanged.
+ *      again no new C symbol — UserShaderArgs, smr_user_shader and its launch, the renderer's registry and the bindings are unchanged;
+ *      animated images (smr_renderer_register_animated_image, smr_animated_frame_index, smr_scene_node_start_pts,
+ *      smr_renderer_image_launches: no struct changed, smr_scene_node keeps its layout, no kernel counter slot was added).
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

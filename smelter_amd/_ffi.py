@@ -50,6 +50,7 @@ EXPORTS = [
     "smr_fontbook_add_dir", "smr_fontbook_count", "smr_fontbook_measure", "smr_fontbook_rasterise", "smr_renderer_set_fontbook",
     "smr_shader_program_create", "smr_shader_program_log", "smr_shader_program_code", "smr_shader_program_launches",
     "smr_shader_program_destroy", "smr_user_shader", "smr_renderer_register_shader_source", "smr_renderer_register_shader_program",
+    "smr_renderer_register_animated_image", "smr_animated_frame_index", "smr_scene_node_start_pts", "smr_renderer_image_launches",
     "smr_abi_version", "smr_build_flags", "smr_sizeof_layout",
 ]
 NO_RESOLUTION = 0xFFFFFFFF
@@ -253,6 +254,10 @@ def load():
         "smr_user_shader": ([P, P, P, C.c_size_t, PP, U, P, F], I),
         "smr_renderer_register_shader_source": ([P, C.c_char_p, C.c_char_p], I),
         "smr_renderer_register_shader_program": ([P, C.c_char_p, P], I),
+        "smr_renderer_register_animated_image": ([P, C.c_char_p, P, U, U, U, C.POINTER(C.c_uint64)], I),
+        "smr_animated_frame_index": ([C.POINTER(C.c_uint64), U, C.c_int64, C.c_int64], I),
+        "smr_scene_node_start_pts": ([P, I, C.POINTER(C.c_int64)], I),
+        "smr_renderer_image_launches": ([P, C.POINTER(C.c_uint64)], I),
         "smr_abi_version": ([], U),
         "smr_build_flags": ([], U),
         "smr_sizeof_layout": ([], U),

@@ -31,13 +31,21 @@ using namespace smr_host;
 #pragma weak smr_ingest_resample_batch
 #pragma weak smr_resample_plan_make
 extern "C" int smr_ctx_device_index(const smr_ctx *ctx) __attribute__((weak));  // smr_ctx.hip; not part of the ABI
+// The image pass's kernel (k_image_nodes, smr_resample.hip; not part of the ABI): n rescales in one launch per 16.  Without the GPU half the
+// pass makes one smr_rescale_bilinear call per job instead.
+extern "C" int smr_image_nodes(smr_ctx *ctx, const smr_surface *const *src, smr_surface *const *dst, uint32_t n) __attribute__((weak));
 
 namespace {
 
 struct ImageRes {
-    smr_surface *surface = nullptr;  // premultiplied RGBA8 node texture at the image's own resolution
+    smr_surface *surface = nullptr;  // premultiplied RGBA8 node texture at the image's own resolution (a static image; null for an animated one)
     uint32_t w = 0, h = 0;
     bool opaque = false;             // every pixel's alpha is 255 (seen at registration; premultiplication keeps the alpha byte)
+    // AnimatedAsset (animated_image.rs:41-118): one such texture per frame, whether that frame is opaque, and the frames' delays
+    std::vector<smr_surface *> frames;
+    std::vector<uint8_t> frame_opaque;
+    std::vector<uint64_t> delays_ns;
+    bool animated() const { return !frames.empty(); }
 };
 
 struct Source {
@@ -99,6 +107,8 @@ struct OutputLane {
     int flip = 0;
     std::vector<smr_surface *> node_surface;   // per graph node, (re)allocated on size change (NodeTexture::ensure_size)
     std::vector<smr_surface *> scaled_image;   // per graph node: an Image node whose size differs from the image's
+    std::vector<uint8_t> image_drawn;          // ... and whether a STATIC image has been drawn into that surface (BitmapNodeState::was_rendered)
+    std::vector<Source> image_source;          // per graph node: what the image pass of this frame left for the walk (Image nodes only)
 };
 
 struct Output {
@@ -133,6 +143,7 @@ struct smr_renderer {
     std::map<std::string, Output> outputs;
     std::string err;
     std::vector<smr_layout> layouts;  // scratch
+    uint64_t image_launches = 0;      // smr_renderer_image_launches
 };
 
 namespace {
@@ -181,6 +192,7 @@ void free_node_surfaces(smr_renderer *r, Output &o) {
         free_shard_slots(r, l);
         l.node_surface.assign(n, nullptr);
         l.scaled_image.assign(n, nullptr);
+        l.image_drawn.assign(n, 0);
     }
     free_surfaces(r, o.text_surface);
     o.text_surface.assign(n, nullptr);
@@ -196,6 +208,7 @@ int enter_lane(smr_renderer *r, Output &o, size_t lane) {
     o.l = &l;
     const size_t n = o.scene.nodes().size();
     if (l.node_surface.size() != n) { l.node_surface.assign(n, nullptr); l.scaled_image.assign(n, nullptr); }
+    if (l.image_drawn.size() != n) l.image_drawn.assign(n, 0);
     if (r->shard_ctx.size() > 1 && l.shard[0].size() != n) { l.shard[0].assign(n, ShardSlot()); l.shard[1].assign(n, ShardSlot()); }
     if (!l.have_frames) {
         int rc = gpu(r, smr_frame_create(r->ctx, o.format, o.w, o.h, &l.frames[0]), "output frame");
@@ -211,10 +224,12 @@ int enter_lane(smr_renderer *r, Output &o, size_t lane) {
 }
 
 // NodeTexture::ensure_size (state/node_texture.rs:22-42)
-int ensure_surface(smr_renderer *r, smr_surface *&slot, uint32_t w, uint32_t h) {
+int ensure_surface(smr_renderer *r, smr_surface *&slot, uint32_t w, uint32_t h, bool *created = nullptr) {
     smr_surface_info info;
+    if (created) *created = false;
     if (slot && smr_surface_info_get(slot, &info) == 0 && info.width == w && info.height == h) return 0;
     if (slot) { smr_surface_destroy(r->ctx, slot); slot = nullptr; }
+    if (created) *created = true;
     return gpu(r, smr_surface_create(r->ctx, w, h, SMR_PX_RGBA8, &slot), "node surface");
 }
 
@@ -361,6 +376,62 @@ static void flatten_shader_param(const Json &j, std::vector<uint8_t> &out) {
     else if (v->kind == Json::Array) for (const Json &e : v->arr) flatten_shader_param(e, out);
 }
 
+// The image pass of one output and frame, before the graph walk.  Every Image node gets its source: the asset itself (a static image) or
+// the frame of this pts on the node's own clock (AnimatedAsset::render, animated_image.rs:120-149) where the node has the asset's size;
+// otherwise the lane's surface of the node's size, into which the asset is drawn bilinearly (bitmap_image.rs:65-88) — an animated one at
+// every render, a static one only until it has been drawn into the surface the lane holds (was_rendered, bitmap_image.rs:71-73).  All the
+// drawing of the pass is ONE smr_image_nodes call: one launch per 16 nodes where there was one per node.
+int image_pass(smr_renderer *r, Output &o, const FrameSetView &fs) {
+    const std::vector<GraphNode> &nodes = o.scene.nodes();
+    OutputLane &l = *o.l;
+    l.image_source.assign(nodes.size(), Source());
+    std::vector<const smr_surface *> src;
+    std::vector<smr_surface *> dst;
+    std::vector<int> job_node;
+    for (int idx = 0; idx < (int)nodes.size(); idx++) {
+        if (nodes[idx].kind != Kind::Image) continue;
+        const Stateful &c = *nodes[idx].component;
+        auto it = r->images.find(c.ref_id);
+        if (it == r->images.end()) continue;
+        const ImageRes &img = it->second;
+        const smr_surface *asset = img.surface;
+        bool opaque = img.opaque;
+        if (img.animated()) {
+            const int k = animated_frame_index(img.delays_ns.data(), (uint32_t)img.delays_ns.size(), fs.pts_ns, c.start_pts_ns);
+            if (k < 0 || k >= (int)img.frames.size()) continue;
+            asset = img.frames[k];
+            opaque = img.frame_opaque[k] != 0;
+        }
+        const uint32_t w = as_u32(c.leaf_size.width), h = as_u32(c.leaf_size.height);
+        Source &out = l.image_source[idx];
+        if (w == img.w && h == img.h) {
+            out.kind = SMR_SOURCE_SURFACE; out.surface = asset; out.w = w; out.h = h; out.opaque = opaque;
+            continue;
+        }
+        if (w == 0 || h == 0) continue;
+        bool created = false;
+        int rc = ensure_surface(r, l.scaled_image[idx], w, h, &created);
+        if (created) l.image_drawn[idx] = 0;
+        if (rc < 0) return rc;
+        if (img.animated() || !l.image_drawn[idx]) { src.push_back(asset); dst.push_back(l.scaled_image[idx]); job_node.push_back(idx); }
+        out.kind = SMR_SOURCE_SURFACE; out.surface = l.scaled_image[idx]; out.w = w; out.h = h;
+    }
+    if (src.empty()) return 0;
+    if (smr_image_nodes) {
+        int rc = gpu(r, smr_image_nodes(r->ctx, src.data(), dst.data(), (uint32_t)src.size()), "image pass");
+        if (rc < 0) return rc;
+        r->image_launches += (src.size() + 15) / 16;
+    } else {
+        for (size_t i = 0; i < src.size(); i++) {
+            int rc = gpu(r, smr_rescale_bilinear(r->ctx, src[i], dst[i]), "image node");
+            if (rc < 0) return rc;
+            r->image_launches++;
+        }
+    }
+    for (int idx : job_node) l.image_drawn[idx] = 1;  // (an animated node is drawn again whatever this says)
+    return 0;
+}
+
 int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Source &out) {
     const GraphNode &g = o.scene.nodes()[idx];
     const Stateful &c = *g.component;
@@ -381,24 +452,9 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
         }
         return 0;
     }
-    case Kind::Image: {
-        auto it = r->images.find(c.ref_id);
-        if (it == r->images.end()) return 0;
-        const uint32_t w = as_u32(c.leaf_size.width), h = as_u32(c.leaf_size.height);
-        if (w == it->second.w && h == it->second.h) {
-            out.kind = SMR_SOURCE_SURFACE; out.surface = it->second.surface; out.w = w; out.h = h; out.opaque = it->second.opaque;
-            return 0;
-        }
-        if (w == 0 || h == 0) return 0;
-        // the image pass draws the asset into the node's own resolution (bitmap_image.rs:65-88): bilinear
-        smr_surface *&dst = o.l->scaled_image[idx];
-        int rc = ensure_surface(r, dst, w, h);
-        if (rc < 0) return rc;
-        rc = gpu(r, smr_rescale_bilinear(r->ctx, it->second.surface, dst), "image node");
-        if (rc < 0) return rc;
-        out.kind = SMR_SOURCE_SURFACE; out.surface = dst; out.w = w; out.h = h;
+    case Kind::Image:
+        out = o.l->image_source[idx];  // drawn, where it had to be, by this frame's image pass
         return 0;
-    }
     case Kind::Text: {
         if (o.text_surface[idx]) {
             out.kind = SMR_SOURCE_SURFACE; out.surface = o.text_surface[idx];
@@ -512,6 +568,7 @@ int render_output(smr_renderer *r, Output &o, const FrameSetView &fs, const smr_
     smr_frame *target = &o.l->frames[o.l->flip];
     *result = target;
     if (o.scene.nodes().empty()) return gpu(r, smr_frame_fill_black(r->ctx, target), "empty output");
+    if (int rc = image_pass(r, o, fs); rc < 0) return rc;
     const GraphNode &root = o.scene.nodes()[0];
     if (root.component->is_layout()) {
         std::vector<Source> kids(root.children.size());
@@ -569,7 +626,8 @@ int render_output(smr_renderer *r, Output &o, const FrameSetView &fs, const smr_
         rgba = o.l->node_surface[0];
     }
     if (s.w != o.w || s.h != o.h) {  // the output converters sample the root texture over the whole output (rgba_to_yuv.rs:74-117)
-        smr_surface *&t = o.l->scaled_image[0];
+        // (a root Image node of its own size was drawn into scaled_image[0] by the image pass: the output-sized copy then takes the other slot)
+        smr_surface *&t = rgba == o.l->scaled_image[0] ? o.l->node_surface[0] : o.l->scaled_image[0];
         rc = ensure_surface(r, t, o.w, o.h);
         if (rc < 0) return rc;
         rc = gpu(r, smr_rescale_bilinear(r->ctx, rgba, t), "root rescale");
@@ -612,8 +670,10 @@ SMR_API void smr_renderer_destroy(smr_renderer *r) {
     if (!r) return;
     sync_lanes(r);
     for (auto &kv : r->outputs) free_output(r, kv.second);
-    for (auto &kv : r->images)
+    for (auto &kv : r->images) {
         if (kv.second.surface) smr_surface_destroy(r->ctx, kv.second.surface);
+        for (smr_surface *f : kv.second.frames) smr_surface_destroy(r->ctx, f);
+    }
     if (r->comm) smr_comm_destroy(r->comm);
     for (auto &kv : r->shaders)
         if (kv.second.hook.release) kv.second.hook.release(kv.second.hook.user);
@@ -659,6 +719,59 @@ SMR_API int smr_renderer_register_image(smr_renderer *r, const char *image_id, c
     for (size_t i = 0, n = (size_t)width * height; i < n && res.opaque; i++) res.opaque = rgba[4 * i + 3] == 255;
     r->images[image_id] = res;
     for (auto &kv : r->outputs) kv.second.scene.register_image(image_id, (float)width, (float)height);
+    return 0;
+}
+
+// AnimatedAsset::new (animated_image.rs:41-118) after the decoder: every frame uploaded and premultiplied once, like BitmapAsset's one
+SMR_API int smr_renderer_register_animated_image(smr_renderer *r, const char *image_id, const uint8_t *rgba, uint32_t width, uint32_t height,
+                                                 uint32_t n_frames, const uint64_t *delays_ns) {
+    if (!r || !image_id) return fail(r, -1, "smr_renderer_register_image: null argument");
+    if (n_frames == 0) return fail(r, -1, "Animated image does not contain any frames.");
+    if (n_frames > 1000) return fail(r, -1, "Detected over 1000 frames inside the animated image. This case is not currently supported.");
+    if (n_frames == 1) return smr_renderer_register_image(r, image_id, rgba, width, height);  // AnimatedAsset's SingleFrame fallback
+    if (!rgba || !width || !height || !delays_ns) return fail(r, -1, "smr_renderer_register_image: null argument");
+    if (r->images.count(image_id)) return fail(r, -1, std::string("Failed to register an image. Image \"") + image_id + "\" is already registered.");
+    uint64_t duration = 0;
+    for (uint32_t k = 0; k < n_frames; k++) {
+        if (delays_ns[k] > (uint64_t)INT64_MAX - duration) return fail(r, -1, "smr_renderer_register_animated_image: the delays add up to more than INT64_MAX ns");
+        duration += delays_ns[k];
+    }
+    ImageRes res;
+    res.w = width; res.h = height;
+    res.delays_ns.assign(delays_ns, delays_ns + n_frames);
+    const size_t frame_px = (size_t)width * height;
+    smr_surface *raw = nullptr;
+    int rc = gpu(r, smr_surface_create(r->ctx, width, height, SMR_PX_RGBA8, &raw), "image upload");
+    for (uint32_t k = 0; k < n_frames && rc >= 0; k++) {
+        const uint8_t *px = rgba + 4 * frame_px * k;
+        smr_surface *pm = nullptr;
+        rc = gpu(r, smr_surface_create(r->ctx, width, height, SMR_PX_RGBA8, &pm), "image upload");
+        if (rc < 0) break;
+        res.frames.push_back(pm);
+        rc = gpu(r, smr_surface_upload(r->ctx, raw, px, (size_t)width * 4), "image upload");
+        if (rc >= 0) rc = gpu(r, smr_add_premultiplied_alpha(r->ctx, raw, pm), "image premultiply");
+        bool opaque = true;
+        for (size_t i = 0; i < frame_px && opaque; i++) opaque = px[4 * i + 3] == 255;
+        res.frame_opaque.push_back(opaque ? 1 : 0);
+    }
+    if (raw) {
+        // (also after a failure, before `raw` goes: a premultiply may still read it)
+        if (rc >= 0) rc = gpu(r, smr_sync(r->ctx), "image upload");
+        else (void)smr_sync(r->ctx);
+        smr_surface_destroy(r->ctx, raw);
+    }
+    if (rc < 0) {
+        for (smr_surface *f : res.frames) smr_surface_destroy(r->ctx, f);
+        return rc;
+    }
+    r->images[image_id] = res;
+    for (auto &kv : r->outputs) kv.second.scene.register_image(image_id, (float)width, (float)height);
+    return 0;
+}
+
+SMR_API int smr_renderer_image_launches(const smr_renderer *r, uint64_t *count) {
+    if (!r || !count) return -1;
+    *count = r->image_launches;
     return 0;
 }
 

@@ -275,6 +275,7 @@ std::unique_ptr<Stateful> Stateful::clone() const {
     c->shader_param = shader_param; c->view_end = view_end; c->view_start = view_start; c->resc_end = resc_end;
     c->resc_start = resc_start; c->tiles = tiles; c->tiles_start = tiles_start; c->tiles_last_layout = tiles_last_layout;
     c->transition = transition;
+    c->image_w = image_w; c->image_h = image_h; c->start_pts_ns = start_pts_ns;
     for (auto &ch : children) c->children.push_back(ch->clone());
     return c;
 }
@@ -739,6 +740,29 @@ void convert_to_shader_color(RGBA c, bool srgb, float out[4]) {  // wgpu/utils.r
         out[0] = (float)(a * (double)c.r / 255.0); out[1] = (float)(a * (double)c.g / 255.0); out[2] = (float)(a * (double)c.b / 255.0);
     }
     out[3] = (float)a;
+}
+
+// ------------------------------------------------------------------------------------------------ animated images
+// AnimatedAsset::render (animated_image.rs:127-136): frames.iter().min_by_key(|f| abs_diff(f.pts, animation_pts)) — the FIRST of equally
+// close frames, and no wrap-around: shortly before the loop ends the last frame shows, not frame 0.  128-bit sums: any uint64 delays are defined.
+int animated_frame_index(const uint64_t *delays_ns, uint32_t n_frames, int64_t pts_ns, int64_t start_pts_ns) {
+    if (!delays_ns || !n_frames) return -1;
+    typedef unsigned __int128 u128;
+    u128 duration = 0;
+    for (uint32_t k = 0; k < n_frames; k++) duration += delays_ns[k];
+    if (duration == 0) duration = 1;  // Duration::from_nanos(1): a GIF without delays
+    // (the reference subtracts unsigned Durations and would underflow on pts < start_pts: here that is time 0)
+    const uint64_t elapsed = pts_ns > start_pts_ns ? (uint64_t)pts_ns - (uint64_t)start_pts_ns : 0u;
+    const u128 t = (u128)elapsed % duration;
+    u128 frame_pts = 0, best_diff = 0;
+    int best = 0;
+    for (uint32_t k = 0; k < n_frames; k++) {
+        const u128 diff = frame_pts > t ? frame_pts - t : t - frame_pts;
+        if (k == 0 || diff < best_diff) { best = (int)k; best_diff = diff; }
+        else if (frame_pts > t) break;  // frame starts only grow from here: nothing closer follows
+        frame_pts += delays_ns[k];
+    }
+    return best;
 }
 
 }  // namespace smr_host

@@ -135,6 +135,8 @@ struct Stateful {
         std::string family, style, weight, wrap, align;
     } text_spec;
     Json shader_param;
+    OptF image_w, image_h;       // Image: the component's own width / height (what "unchanged" compares, image_component.rs:91-120)
+    int64_t start_pts_ns = 0;    // Image: ImageRenderParams::start_pts — kept across updates while the component is unchanged, else the last render's pts
     Json desc;                   // the converted component (scene::Component) as canonical JSON, see Scene::parse
     // layouts
     ViewParam view_end; std::optional<ViewParam> view_start;
@@ -275,6 +277,9 @@ class Scene {
     uint32_t out_w_ = 0, out_h_ = 0;
 };
 
+// AnimatedAsset::render's frame choice (transformations/image/animated_image.rs:120-149), exact integers: the frame whose start is closest to
+// (pts - start_pts, clamped at 0) mod (sum of the delays, 1 ns if that is 0), the first one on a tie, no wrap-around.  -1 without frames.
+int animated_frame_index(const uint64_t *delays_ns, uint32_t n_frames, int64_t pts_ns, int64_t start_pts_ns);
 void convert_to_shader_color(RGBA c, bool srgb, float out[4]);  // wgpu/utils.rs:51-81
 bool parse_color(const std::string &s, RGBA &out, std::string &err);  // smelter-api/src/video/color.rs
 

@@ -522,6 +522,10 @@ std::unique_ptr<Stateful> build(const Json &j, BuildCtx &c) {
         else if (h) { rw = as_usize(std::round(*h * aspect)); rh = as_usize(std::round(*h)); }
         else { rw = iw; rh = ih; }
         s->leaf_size = {(float)rw, (float)rh};
+        // ImageComponent::stateful_component (image_component.rs:91-120): the clock of an unchanged component runs on across the update
+        s->image_w = w; s->image_h = h;
+        const Stateful *prev = previous(*s, Kind::Image, c);
+        s->start_pts_ns = prev && prev->ref_id == s->ref_id && prev->image_w == w && prev->image_h == h ? prev->start_pts_ns : c.last_pts;
         return s;
     }
     if (t == "text") {  // text_component.rs; only TextDimensions::Fixed can be sized without the text shaper

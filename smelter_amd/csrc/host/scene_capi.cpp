@@ -108,6 +108,20 @@ SMR_API int smr_scene_node_layouts(smr_scene *scene, int node, int64_t pts_ns, c
     return 0;
 }
 
+SMR_API int smr_scene_node_start_pts(const smr_scene *scene_c, int node, int64_t *start_pts_ns) {
+    smr_scene *scene = const_cast<smr_scene *>(scene_c);
+    if (!scene || !start_pts_ns) return set_err(scene, "smr_scene_node_start_pts: null argument");
+    const auto &nodes = scene->scene.nodes();
+    if (node < 0 || node >= (int)nodes.size()) return set_err(scene, "smr_scene_node_start_pts: node index out of range");
+    if (nodes[node].kind != Kind::Image) return set_err(scene, "smr_scene_node_start_pts: not an Image node");
+    *start_pts_ns = nodes[node].component->start_pts_ns;
+    return 0;
+}
+
+SMR_API int smr_animated_frame_index(const uint64_t *delays_ns, uint32_t n_frames, int64_t pts_ns, int64_t start_pts_ns) {
+    return animated_frame_index(delays_ns, n_frames, pts_ns, start_pts_ns);
+}
+
 SMR_API double smr_cubic_bezier_easing(double progress, double x1, double y1, double x2, double y2) {
     return cubic_bezier_easing(progress, x1, y1, x2, y2);
 }

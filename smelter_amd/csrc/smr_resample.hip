@@ -9,6 +9,7 @@
 // weight table per output coordinate, built once per workgroup in LDS and shared by the
 // 64 threads that walk the perpendicular axis.
 #include "smr_resample_dev.h"
+#include "smr_image_nodes.h"
 
 #include <cmath>
 
@@ -341,6 +342,35 @@ int smr_rescale_bilinear(smr_ctx *ctx, const smr_surface *src, smr_surface *dst)
     hipLaunchKernelGGL(k_rescale_bilinear, grid, dim3(256), 0, ctx->stream, view_of(src), view_of(dst), pxi_of(ctx, src),
                        ctx->d_tables);
     return smr_check_hip(ctx, hipGetLastError(), "k_rescale_bilinear");
+}
+
+// smr_rescale_bilinear for n (source, destination) pairs at once — the renderer's image pass (host/renderer.cpp; not part of smr.h): one
+// launch of k_image_nodes per 16 pairs, the bytes smr_rescale_bilinear writes.  No kernel counter slot: smr_renderer_image_launches counts.
+__attribute__((visibility("default"))) int smr_image_nodes(smr_ctx *ctx, const smr_surface *const *src, smr_surface *const *dst, uint32_t n) {
+    SMR_ENTER(ctx);
+    if (!ctx || (n && (!src || !dst))) return SMR_ERR_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!src[i] || !dst[i] || !src[i]->ptr || !dst[i]->ptr || !src[i]->w || !src[i]->h || !dst[i]->w || !dst[i]->h)
+            return smr_fail(ctx, SMR_ERR_INVALID, "smr_image_nodes: pair %u lacks a surface", i);
+        if (src[i]->fmt != SMR_PX_RGBA8 || dst[i]->fmt != SMR_PX_RGBA8) return smr_fail(ctx, SMR_ERR_INVALID, "smr_image_nodes: surfaces must be RGBA8");
+        if (src[i] == dst[i]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_image_nodes: pair %u draws a surface into itself", i);
+    }
+    StageScope scope(ctx, SMR_STAGE_RESAMPLE);
+    for (uint32_t at = 0; at < n; at += SMR_IMAGE_MAX_JOBS) {
+        ImageBatch B;
+        memset(&B, 0, sizeof(B));
+        B.n = n - at < SMR_IMAGE_MAX_JOBS ? n - at : SMR_IMAGE_MAX_JOBS;
+        for (u32 i = 0; i < B.n; i++) {
+            B.j[i].src = view_of(src[at + i]);
+            B.j[i].dst = view_of(dst[at + i]);
+            B.j[i].pxi = pxi_of(ctx, src[at + i]);
+        }
+        const u32 blocks = in_plan(B);
+        if (!blocks) continue;
+        hipLaunchKernelGGL(k_image_nodes, dim3(blocks), dim3(SMR_IMAGE_BLOCK), 0, ctx->stream, B, ctx->d_tables);
+        SMR_HIP(ctx, hipGetLastError());
+    }
+    return SMR_OK;
 }
 
 

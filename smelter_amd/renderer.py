@@ -96,6 +96,24 @@ class Renderer:
         h, w = px.shape[:2]
         self._check(self.lib.smr_renderer_register_image(self._h, image_id.encode(), px.ctypes.data, w, h))
 
+    def register_animated_image(self, image_id: str, frames: np.ndarray, delays_ns: Sequence[int]):
+        """The decoded frames of an animated image, `frames[n, h, w, 4]` straight-alpha RGBA8, and their delays in ns
+        (smr_renderer_register_animated_image): an Image node of it shows the frame of the render's pts on the node's own clock."""
+        px = np.ascontiguousarray(frames, dtype=np.uint8)
+        if px.ndim != 4 or px.shape[3] != 4:
+            raise ValueError("frames must be [n, h, w, 4]")
+        n, h, w = px.shape[:3]
+        if len(delays_ns) != n:
+            raise ValueError("one delay per frame")
+        delays = (C.c_uint64 * max(n, 1))(*[int(d) for d in delays_ns])
+        self._check(self.lib.smr_renderer_register_animated_image(self._h, image_id.encode(), px.ctypes.data, w, h, n, delays))
+
+    def image_launches(self) -> int:
+        """Launches of the image pass so far, all lanes (smr_renderer_image_launches)."""
+        n = C.c_uint64()
+        self._check(self.lib.smr_renderer_image_launches(self._h, C.byref(n)))
+        return n.value
+
     def set_text_measurer(self, measurer):
         """The caller's text shaper for Text nodes without explicit width / height (tests.text_twin.Shaper(...).measurer)."""
         self._measurer = measurer  # keep the callback alive

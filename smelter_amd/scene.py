@@ -88,6 +88,12 @@ class Scene:
                             (info.ref_id or b"").decode(), (info.id or b"").decode(), (info.payload or b"").decode()))
         return out
 
+    def node_start_pts(self, node: int) -> int:
+        """start_pts (ns) of Image node `node`: the pts its animation clock counts from (smr_scene_node_start_pts)."""
+        out = C.c_int64()
+        self._check(self._lib.smr_scene_node_start_pts(self._h, node, C.byref(out)))
+        return out.value
+
     def node_layouts(self, node: int, pts_ns: int, child_resolutions: Sequence[Optional[Tuple[int, int]]],
                      mode: int = MODE_GPU_OPTIMIZED, cap: int = 512):
         """-> (ctypes array of smr_layout, count, out_w, out_h) for layout node `node` at `pts_ns`."""
@@ -141,6 +147,16 @@ class Layout:
         masks = [Mask(list(m.radius), m.top, m.left, m.width, m.height) for m in s.masks[: s.masks_len]]
         return Layout(s.top, s.left, s.width, s.height, s.rotation_degrees, list(s.border_radius), s.type, s.source_index,
                       list(s.color), list(s.border_color), s.border_width, list(s.crop), s.blur_radius, masks)
+
+
+def animated_frame_index(delays_ns: Sequence[int], pts_ns: int, start_pts_ns: int = 0) -> int:
+    """The frame an animated image shows at `pts_ns` on a clock started at `start_pts_ns` (smr_animated_frame_index)."""
+    n = len(delays_ns)
+    arr = (C.c_uint64 * max(n, 1))(*[int(d) for d in delays_ns])
+    k = _ffi.load().smr_animated_frame_index(arr, n, int(pts_ns), int(start_pts_ns))
+    if k < 0:
+        raise SceneError("Animated image does not contain any frames.")
+    return k
 
 
 def cubic_bezier_easing(progress: float, x1: float, y1: float, x2: float, y2: float) -> float:
