@@ -31,6 +31,7 @@ using namespace smr_host;
 #pragma weak smr_ingest_resample_batch
 #pragma weak smr_resample_plan_make
 extern "C" int smr_ctx_device_index(const smr_ctx *ctx) __attribute__((weak));  // smr_ctx.hip; not part of the ABI
+extern "C" uint32_t smr_ctx_drawn_layouts(const smr_ctx *ctx, uint32_t n) __attribute__((weak));  // smr_ctx.hip; not part of the ABI
 // The image pass's kernel (k_image_nodes, smr_resample.hip; not part of the ABI): n rescales in one launch per 16.  Without the GPU half the
 // pass makes one smr_rescale_bilinear call per job instead.
 extern "C" int smr_image_nodes(smr_ctx *ctx, const smr_surface *const *src, smr_surface *const *dst, uint32_t n) __attribute__((weak));
@@ -66,10 +67,12 @@ bool frame_opaque(const smr_frame *f) { return f && f->format <= SMR_FRAME_NV12;
 // is opaque: bilinear weights are 8-bit fractions and sum to 1 exactly, so an opaque texture samples alpha exactly 1 —, has no rotation, rounded
 // corner, border or mask, lies on half-integer coordinates (the coverage arithmetic is then exact) and covers every pixel centre by at least half
 // a pixel: its fragment's alpha is exactly 1 there, and whatever is blended above leaves src.a + 1 * (1 - src.a), which stores 255.
-// Conservative: `false` only costs the compositor its shortcut.
-bool layouts_leave_an_opaque_surface(const std::vector<smr_layout> &layouts, const std::vector<Source> &kids, uint32_t w, uint32_t h) {
+// Only the first `drawn` layouts count: the compositor skips what lies beyond the context's max_layouts (smr_render_layouts), and a cover
+// in that tail is never drawn.  Conservative: `false` only costs the compositor its shortcut.
+bool layouts_leave_an_opaque_surface(const std::vector<smr_layout> &layouts, size_t drawn, const std::vector<Source> &kids, uint32_t w, uint32_t h) {
     auto half_int = [](float v) { return v * 2.0f == std::floor(v * 2.0f) && std::fabs(v) < 32768.0f; };
-    for (const smr_layout &L : layouts) {
+    for (size_t i = 0; i < layouts.size() && i < drawn; i++) {
+        const smr_layout &L = layouts[i];
         if (L.rotation_degrees != 0.0f || L.border_width != 0.0f || L.masks_len != 0) continue;
         if (L.border_radius[0] != 0.0f || L.border_radius[1] != 0.0f || L.border_radius[2] != 0.0f || L.border_radius[3] != 0.0f) continue;
         if (L.type == 1) {
@@ -550,7 +553,9 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
     std::string err;
     if (!o.scene.node_layouts(idx, fs.pts_ns, res, smr_ctx_mode(r->ctx) == SMR_MODE_GPU_OPTIMIZED, r->layouts, w, h, err)) return fail(r, -1, err);
     if (w == 0 || h == 0) return 0;
-    const bool node_opaque = layouts_leave_an_opaque_surface(r->layouts, kids, w, h);
+    // (without the GPU half — tests/san — nothing is drawn at all and the whole list is scanned)
+    const size_t drawn = smr_ctx_drawn_layouts ? smr_ctx_drawn_layouts(r->ctx, (uint32_t)r->layouts.size()) : r->layouts.size();
+    const bool node_opaque = layouts_leave_an_opaque_surface(r->layouts, drawn, kids, w, h);
     int rc = ensure_surface(r, o.l->node_surface[idx], w, h);
     if (rc < 0) return rc;
     rc = shard_layout_sources(r, o, kids, srcs);

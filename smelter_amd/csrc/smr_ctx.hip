@@ -314,6 +314,14 @@ int smr_profile_read(smr_ctx *ctx, int stage, float *total_ms, uint32_t *launche
 // the HIP device of a context: for the renderer (host/renderer.cpp, smr_renderer_add_shard), not part of the ABI
 int smr_ctx_device_index(const smr_ctx *ctx) { return ctx ? ctx->device : -1; }
 
+// how many layouts of a list of n this context draws (smr_render_layouts / smr_pack_layouts skip the rest, params.rs:176-182): for the
+// renderer's claims about what a layout node leaves behind (host/renderer.cpp), not part of the ABI
+uint32_t smr_ctx_drawn_layouts(const smr_ctx *ctx, uint32_t n) {
+    if (!ctx) return 0;
+    if (n > ctx->max_layouts) n = ctx->max_layouts;
+    return n > (uint32_t)SMR_SLOT_MAX_LAYOUTS ? (uint32_t)SMR_SLOT_MAX_LAYOUTS : n;
+}
+
 int smr_debug_kernel_launches(const smr_ctx *ctx, uint32_t kernel, uint64_t *count) {
     if (!ctx || !count || kernel >= SMR_KERNEL_COUNT_) return SMR_ERR_INVALID;
     *count = ctx->kernel_launches[kernel];

@@ -277,8 +277,8 @@ class Context:
         return lab_build()
 
     def set_plane_source(self, on: bool):
-        """SMR_OPT_PLANE_SOURCE: 4:2:0 frames are converted inside the matrix-core resampler (exactly, through LDS; default on) or by the converter
-        kernel into a node texture in memory (off) — the same pixels."""
+        """SMR_OPT_PLANE_SOURCE: 4:2:0 frames are converted inside the matrix-core resampler (exactly, through LDS; opt-in: it measured slower)
+        or by the converter kernel into a node texture in memory (off, the default) — the same pixels."""
         self.set_option(OPT_PLANE_SOURCE, 1 if on else 0)
 
     def set_direct_output(self, on: bool):

@@ -2,7 +2,8 @@
 CPU by tests/emu/emu_compose.cpp and launched as smr_render_layouts launches them (the host's own packing of the layout list, the tile
 classes, the band list + every tile), against the oracle's apply_layouts + rgba_to_yuv / rgba_to_nv12: EVERY BYTE EQUAL — the compositor
 adds no rounding of its own to the tile's bytes, whatever class a tile falls into.  Test infrastructure only: the
-product has no CPU path; tests/test_gpu_fused.py and tests/test_gpu_reference_scenes.py hold the kernel itself to the oracle on the device."""
+product has no CPU path; tests/test_gpu_compose_zoo.py holds the kernel itself to the oracle on the device, on the same lists from the same
+seeds (tests/compose_zoo.py); tests/test_gpu_fused.py and tests/test_gpu_reference_scenes.py add the benchmark scenes and the reference's corpus."""
 import ctypes as C
 import os
 import subprocess
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests.compose_zoo import grid_scene as _grid_scene, tex as _tex, video as _video, zoo as _zoo  # (shared with tests/test_gpu_compose_zoo.py)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 EMU = os.path.join(HERE, "emu")
@@ -76,44 +78,6 @@ def assert_same(got, want, what):
     for k, (g, w) in enumerate(zip(got, want)):
         w = np.asarray(w).reshape(g.shape)
         assert np.array_equal(g, w), (what, "plane", k, int((g != w).sum()), np.argwhere(g != w)[:5].tolist())
-
-
-def _video(w, h, seed, alpha=False):
-    """An opaque 'resampled tile' (noise on a gradient: every texel differs from its neighbours), or with `alpha` a premultiplied one."""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    t = np.stack([(xx * 3 + seed * 40) % 256, (yy * 5 + 90) % 256, (xx + yy * 2) % 256, np.full_like(xx, 255)], -1).astype(np.int64)
-    t[..., :3] = np.clip(t[..., :3] + rng.integers(-20, 21, (h, w, 3)), 0, 255)
-    if alpha:
-        a = rng.integers(0, 256, (h, w))
-        t = np.concatenate([t[..., :3] * a[..., None] // 255, a[..., None]], -1)
-    return t.astype(np.uint8)
-
-
-def _tex(i, left, top, w, h, tw=None, th=None, **kw):
-    tw, th = tw or int(w), th or int(h)
-    return orc.Layout(top=top, left=left, width=w, height=h, type=0, source_index=i, crop=(0.0, 0.0, float(tw), float(th)), **kw)
-
-
-def _grid_scene(W, H, cols, rows, gap=0, srgb=True, labels=True):
-    """BASELINE configs[2] in small: a background colour, a grid of opaque tiles blitted 1:1 (texture / select / colour / clear tiles), and
-    translucent rounded labels with a border over the lower left corners of every other one (composited tiles)."""
-    tw, th = (W - gap * (cols + 1)) // cols, (H - gap * (rows + 1)) // rows
-    layouts = [orc.Layout(top=0.0, left=0.0, width=float(W), height=float(H), type=1, color=orc.color_to_shader((16, 24, 48, 255), srgb))]
-    sources, kinds = [], []
-    for r in range(rows):
-        for c in range(cols):
-            if r == rows - 1 and c == cols - 1:
-                continue  # the last cell stays background
-            i = len(sources)
-            sources.append(_video(tw, th, i))
-            kinds.append(2)
-            left, top = gap + c * (tw + gap), gap + r * (th + gap)
-            layouts.append(_tex(i, float(left), float(top), float(tw), float(th)))
-            if labels and i % 2 == 0:
-                layouts.append(orc.Layout(top=float(top + th - 22), left=float(left + 6), width=70.0, height=16.0, type=1, border_radius=(5.0,) * 4,
-                                          color=orc.color_to_shader((0, 0, 0, 150), srgb), border_width=1.0, border_color=orc.color_to_shader((255, 255, 255, 200), srgb)))
-    return layouts, sources, kinds
 
 
 @pytest.mark.parametrize("out", ["planar", "nv12", "rgba"])
@@ -197,28 +161,6 @@ def test_a_tile_at_its_own_size_and_a_fractional_position_shares_texels_between_
     got, classes = compose(emu, layouts, sources, [2], W, H, "planar", srgb=srgb)
     assert_same(got, oracle_output(layouts, sources, W, H, "planar", srgb), (left, top, srgb, classes))
     assert classes["sampled"] > 0, classes
-
-
-def _zoo(W, H, rng, n, n_sources, srgb=True):
-    layouts = []
-    for _ in range(n):
-        t = int(rng.integers(0, 3))
-        w, h = float(rng.uniform(8, W * 0.7)), float(rng.uniform(6, H * 0.9))
-        rmax = min(w, h) / 2
-        L = orc.Layout(top=float(rng.uniform(-10, H - 4)), left=float(rng.uniform(-20, W - 8)), width=w, height=h, type=t,
-                       rotation_degrees=float(rng.choice([0.0, 0.0, 0.0, 17.0, -33.5, 90.0])),
-                       border_radius=tuple(float(rng.uniform(0, rmax)) if rng.random() < 0.5 else 0.0 for _ in range(4)),
-                       color=orc.color_to_shader(tuple(int(v) for v in rng.integers(0, 256, 3)) + (int(rng.choice([255, 255, 140, 0])),), srgb),
-                       border_color=orc.color_to_shader(tuple(int(v) for v in rng.integers(0, 256, 4)), srgb),
-                       border_width=float(rng.choice([0.0, 0.0, 0.5, 1.0, 3.5])), blur_radius=float(rng.choice([0.0, 2.0, 9.0])) if t == 2 else 0.0)
-        if t == 0:
-            L.source_index = int(rng.integers(0, n_sources + 1))   # (n_sources: out of range = the empty texture)
-            L.crop = (float(rng.uniform(0, 6)), float(rng.uniform(0, 9)), float(rng.uniform(20, 90)), float(rng.uniform(10, 50)))
-        if rng.random() < 0.4:
-            L.masks = [orc.Mask(radius=(float(rng.uniform(0, 12)),) * 4, top=float(rng.uniform(0, H / 2)), left=float(rng.uniform(0, W / 2)),
-                                width=float(rng.uniform(W / 4, W)), height=float(rng.uniform(H / 4, H))) for _ in range(int(rng.integers(1, 4)))]
-        layouts.append(L)
-    return layouts
 
 
 @pytest.mark.parametrize("seed", range(6))
