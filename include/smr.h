@@ -608,7 +608,8 @@ typedef enum smr_node_kind {
     SMR_NODE_LAYOUT = 1,       /* NodeParams::Layout (View / Rescaler / Tiles root) */
     SMR_NODE_TEXT = 2,         /* NodeParams::Text */
     SMR_NODE_IMAGE = 3,        /* NodeParams::Image */
-    SMR_NODE_SHADER = 4        /* NodeParams::Shader */
+    SMR_NODE_SHADER = 4,       /* NodeParams::Shader */
+    SMR_NODE_WEB_VIEW = 5      /* NodeParams::Web: size = the instance's resolution, children as a Shader's */
 } smr_node_kind;
 
 typedef struct smr_scene_node {
@@ -616,7 +617,7 @@ typedef struct smr_scene_node {
     int32_t parent;       /* -1 for the root */
     uint32_t n_children;
     uint32_t width, height; /* intrinsic size (0,0 for an input stream that has not rendered yet) */
-    const char *ref_id;   /* input_id / image_id / shader_id, "" for layouts and text; valid until the next update */
+    const char *ref_id;   /* input_id / image_id / shader_id / instance_id, "" for layouts and text; valid until the next update */
     const char *id;       /* component id or "" */
     const char *payload;  /* Text: the string; otherwise "" */
 } smr_scene_node;
@@ -637,6 +638,12 @@ typedef int (*smr_text_measure_fn)(void *user, const smr_text_params *params, fl
 SMR_API int smr_scene_set_text_measurer(smr_scene *scene, smr_text_measure_fn fn, void *user);
 /* Renderer::register_renderer(Image) as far as sizing goes (scene/image_component.rs) */
 SMR_API int smr_scene_register_image(smr_scene *scene, const char *image_id, uint32_t width, uint32_t height);
+/* Renderer::register_renderer(WebRenderer) as far as the scene goes: with it a `web_view` of this instance builds — a node of kind
+ * SMR_NODE_WEB_VIEW whose size is width x height (web_view_component.rs:23-25, scene_state.rs:205) and whose children are built and walked
+ * as a Shader's (a layout child needs a known size).  The reference's three errors, in its words (scene.rs:208-219): an instance that is
+ * not registered, a child without an "id", and an instance used by more than one component of the scene (validation.rs:74-99; the renderer
+ * holds the same rule across all its outputs).  Registering an id again replaces its resolution. */
+SMR_API int smr_scene_register_web_renderer(smr_scene *scene, const char *instance_id, uint32_t width, uint32_t height);
 /* Renderer::update_scene (state.rs:177-189).  On error the previous scene stays active. */
 SMR_API int smr_scene_update(smr_scene *scene, const char *scene_json, uint32_t out_width, uint32_t out_height);
 /* The API-to-scene conversion alone: `impl TryFrom<Component> for scene::Component`
@@ -678,6 +685,8 @@ SMR_API int smr_parse_color(const char *text, uint8_t rgba[4]);
  *                                 smr_renderer_register_animated_image (the decoded frames of a GIF and their delays)
  *   register_renderer(Shader)  -> smr_renderer_register_shader (a built-in kernel id), smr_renderer_register_shader_source /
  *                                 _program (a user shader written in HIP C++; WGSL text is out of scope)
+ *   register_renderer(WebRenderer) -> smr_renderer_register_web_renderer + smr_renderer_web_paint / _web_positions (the page's pixels and
+ *                                 the children's rectangles are the caller's; the node's compositing is here: "WebView nodes" below)
  *   update_scene               -> smr_renderer_update_scene(output_id, resolution, OutputFrameFormat, scene JSON) (state.rs:177-189)
  *   render(FrameSet<InputId>)  -> smr_renderer_render: populate_inputs (stale frames dropped), depth-first walk of every output's
  *                                 render graph (input refs, images, text, shader and nested layout nodes), read_outputs fused
@@ -718,6 +727,46 @@ SMR_API int smr_renderer_register_animated_image(smr_renderer *r, const char *im
  * pass runs once per output and render, before the graph walk: every Image node whose size differs from its asset's is drawn into the
  * node's resolution — animated assets at every render, static ones once per node surface — by ONE launch per 16 such nodes. */
 SMR_API int smr_renderer_image_launches(const smr_renderer *r, uint64_t *count);
+/* WebView nodes: the compositing half of the reference's web renderer (transformations/web_renderer/renderer.rs:78-134, shader.rs:53-114,
+ * render_website.wgsl).  The browser is the caller's — no CEF, no process, no shared memory here: a host that
+ * owns one registers an instance, hands over the latest paint and the latest rectangles of the children, and a `web_view` component of that
+ * instance draws.  "Decoding is the caller's", as for images.
+ *   register_renderer(WebRenderer)  -> smr_renderer_register_web_renderer: WebRendererSpec's resolution and embedding_method
+ *                                      (web_renderer.rs; renderer.rs:43-76).  SMR_ERR_INVALID: a null or registered id, a zero size, a size
+ *                                      above MAX_NODE_RESOLUTION (7682 x 4320, types.rs:146-149), an unknown method.
+ *   RenderHandler::on_paint         -> smr_renderer_web_paint (browser_client.rs:96-130): width x height premultiplied BGRA8 texels in caller
+ *                                      memory, rows pitch_bytes apart (0 = tight; below 4 * width is refused).  The bitmap is copied before
+ *                                      the call returns, into pinned staging (smr_host_alloc); each lane uploads it with a stream-ordered copy
+ *                                      (smr_frame_upload_async's) at its next render of the node when its own copy is older.  The latest
+ *                                      paint wins; nothing blocks the host.
+ *   GET_FRAME_POSITIONS' reply      -> smr_renderer_web_positions (browser_client.rs:60-93): one rectangle per child in child order, in page
+ *                                      pixels, axis-aligned (the reference's always are: rotation_degrees: 0.0).  n may be 0.
+ * Until the first paint the node has no texture (renderer.rs:89, retrieve_frame) and its parent samples transparent.  After one, every
+ * render redraws the node at the instance's resolution: children zipped with the rectangles (renderer.rs:105-114: a child beyond n is not
+ * drawn, a rectangle beyond the children is ignored, before the first smr_renderer_web_positions nothing but the page is), layered by the
+ * embedding method (renderer.rs:119-131): over content — page, then children in order; under content — children, then the page; Chromium
+ * embedding — the page alone (sending the children's pixels to the browser is out of scope; they are still rendered by the graph walk).
+ * The first layer lands on a transparent target, every later one is blended with PREMULTIPLIED_ALPHA_BLENDING onto the 8-bit target — by
+ * ONE launch per node and 16 children (k_web_view) where the reference makes a render pass per layer.  A child covers pixel (px, py) iff
+ * x <= px + 0.5 < x + width and likewise in y; it is sampled bilinearly, clamped to its edge.  Input-stream children become node textures
+ * first, as a Shader's do; a child without a texture draws nothing.  The node renders on the renderer's own context (lanes keep a page copy
+ * each; with shards it is the root), in both rendering modes, and its output is never treated as opaque.
+ * smr_renderer_unregister_web_renderer is refused while a scene uses the instance. */
+typedef enum smr_web_embedding {
+    SMR_WEB_CHROMIUM_EMBEDDING = 0,   /* WebEmbeddingMethod::ChromiumEmbedding */
+    SMR_WEB_NATIVE_OVER_CONTENT = 1,  /* WebEmbeddingMethod::NativeEmbeddingOverContent */
+    SMR_WEB_NATIVE_UNDER_CONTENT = 2  /* WebEmbeddingMethod::NativeEmbeddingUnderContent */
+} smr_web_embedding;
+typedef struct smr_web_rect {
+    float x, y, width, height; /* getBoundingClientRect of the child's element, page pixels */
+} smr_web_rect;
+SMR_API int smr_renderer_register_web_renderer(smr_renderer *r, const char *instance_id, uint32_t width, uint32_t height, uint32_t embedding);
+SMR_API int smr_renderer_unregister_web_renderer(smr_renderer *r, const char *instance_id);
+SMR_API int smr_renderer_web_paint(smr_renderer *r, const char *instance_id, const uint8_t *bgra_premultiplied, size_t pitch_bytes);
+SMR_API int smr_renderer_web_positions(smr_renderer *r, const char *instance_id, const smr_web_rect *rects, uint32_t n);
+/* k_web_view launches so far, all lanes: one per WebView node and render with up to 16 children, one more per further 16 (modelled on
+ * smr_renderer_image_launches: no kernel counter slot). */
+SMR_API int smr_renderer_web_launches(const smr_renderer *r, uint64_t *count);
 SMR_API int smr_renderer_register_shader(smr_renderer *r, const char *shader_id, uint32_t builtin_id);
 /* A user shader ("user shaders" above) under `shader_id`; registering an id again replaces what it named (built-in or not).
  * _source compiles (blocking, host only) and the renderer owns the program; a source that does not compile fails with the status of
@@ -786,7 +835,10 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      (SMR_DERIVATIVES: smr_dpdx, smr_dpdy, smr_fwidth and their _fine / _coarse forms, on 2 x 2 pixel quads with helper invocations):
  *      again no new C symbol — UserShaderArgs, smr_user_shader and its launch, the renderer's registry and the bindings are unchanged;
  *      animated images (smr_renderer_register_animated_image, smr_animated_frame_index, smr_scene_node_start_pts,
- *      smr_renderer_image_launches: no struct changed, smr_scene_node keeps its layout, no kernel counter slot was added).
+ *      smr_renderer_image_launches: no struct changed, smr_scene_node keeps its layout, no kernel counter slot was added);
+ *      WebView nodes (smr_scene_register_web_renderer, smr_renderer_register_web_renderer / _unregister_web_renderer, smr_renderer_web_paint,
+ *      smr_renderer_web_positions, smr_renderer_web_launches, smr_web_rect, smr_web_embedding, SMR_NODE_WEB_VIEW = 5: a node kind no
+ *      version-2 scene could produce — `web_view` was refused —, no struct changed, no kernel counter slot was added).
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

@@ -51,10 +51,18 @@ EXPORTS = [
     "smr_shader_program_create", "smr_shader_program_log", "smr_shader_program_code", "smr_shader_program_launches",
     "smr_shader_program_destroy", "smr_user_shader", "smr_renderer_register_shader_source", "smr_renderer_register_shader_program",
     "smr_renderer_register_animated_image", "smr_animated_frame_index", "smr_scene_node_start_pts", "smr_renderer_image_launches",
+    "smr_scene_register_web_renderer", "smr_renderer_register_web_renderer", "smr_renderer_unregister_web_renderer", "smr_renderer_web_paint",
+    "smr_renderer_web_positions", "smr_renderer_web_launches",
     "smr_abi_version", "smr_build_flags", "smr_sizeof_layout",
 ]
 NO_RESOLUTION = 0xFFFFFFFF
 NODE_INPUT_STREAM, NODE_LAYOUT, NODE_TEXT, NODE_IMAGE, NODE_SHADER = 0, 1, 2, 3, 4
+NODE_WEB_VIEW = 5
+WEB_CHROMIUM_EMBEDDING, WEB_NATIVE_OVER_CONTENT, WEB_NATIVE_UNDER_CONTENT = 0, 1, 2  # smr_web_embedding
+
+
+class WebRect(C.Structure):  # smr_web_rect
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("width", C.c_float), ("height", C.c_float)]
 
 
 class SceneNode(C.Structure):
@@ -258,6 +266,12 @@ def load():
         "smr_animated_frame_index": ([C.POINTER(C.c_uint64), U, C.c_int64, C.c_int64], I),
         "smr_scene_node_start_pts": ([P, I, C.POINTER(C.c_int64)], I),
         "smr_renderer_image_launches": ([P, C.POINTER(C.c_uint64)], I),
+        "smr_scene_register_web_renderer": ([P, C.c_char_p, U, U], I),
+        "smr_renderer_register_web_renderer": ([P, C.c_char_p, U, U, U], I),
+        "smr_renderer_unregister_web_renderer": ([P, C.c_char_p], I),
+        "smr_renderer_web_paint": ([P, C.c_char_p, P, C.c_size_t], I),
+        "smr_renderer_web_positions": ([P, C.c_char_p, C.POINTER(WebRect), U], I),
+        "smr_renderer_web_launches": ([P, C.POINTER(C.c_uint64)], I),
         "smr_abi_version": ([], U),
         "smr_build_flags": ([], U),
         "smr_sizeof_layout": ([], U),

@@ -11,7 +11,9 @@
 // samples the tile where a single context would have made it itself — the same bytes.  Whatever does not fit that rule (a 1:1 input, one
 // sampled twice, a Shader node's child, the output's root, SMR_MODE_CPU_OPTIMIZED) has its raw planes moved to a root-resident frame by the
 // same gather and is rendered exactly as on one context.
+#include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <map>
@@ -35,8 +37,42 @@ extern "C" uint32_t smr_ctx_drawn_layouts(const smr_ctx *ctx, uint32_t n) __attr
 // The image pass's kernel (k_image_nodes, smr_resample.hip; not part of the ABI): n rescales in one launch per 16.  Without the GPU half the
 // pass makes one smr_rescale_bilinear call per job instead.
 extern "C" int smr_image_nodes(smr_ctx *ctx, const smr_surface *const *src, smr_surface *const *dst, uint32_t n) __attribute__((weak));
+// A WebView node's kernel (k_web_view, smr_layout.hip; not part of the ABI): the page and n children in one launch per 16 children.  Without
+// the GPU half nothing is drawn (as everywhere else there).  The page's way to the device — pinned staging, a stream-ordered copy, "is this
+// context's stream idle" (smr_ctx.hip; not part of the ABI) — is weak for the same reason: staging is then plain memory and nothing is copied.
+extern "C" int smr_web_view(smr_ctx *ctx, const void *page, size_t page_pitch, smr_surface *dst, const smr_surface *const *srcs, const smr_web_rect *rects,
+                            uint32_t n, int under) __attribute__((weak));
+extern "C" int smr_ctx_stream_idle(smr_ctx *ctx) __attribute__((weak));
+#pragma weak smr_host_alloc
+#pragma weak smr_host_free
+#pragma weak smr_frame_upload_async
 
 namespace {
+
+// MAX_NODE_RESOLUTION (smelter-render/src/types.rs:146-149)
+constexpr uint32_t MAX_NODE_W = 7682, MAX_NODE_H = 4320;
+
+// One registered web renderer instance (transformations/web_renderer/renderer.rs:27-35): the spec, the latest paint (frame_data) in pinned
+// staging, the latest rectangles (source_transforms) and, per lane, the page as that lane's context last uploaded it (website_texture).
+struct WebStaging {
+    void *host = nullptr;             // w * 4 * h bytes, tight rows
+    bool pinned = false;              // from smr_host_alloc (else plain memory: no GPU half)
+    std::vector<smr_ctx *> in_flight; // contexts that queued an upload from it and were not seen idle since
+};
+struct WebLanePage {
+    smr_frame page = {};              // SMR_FRAME_BGRA: the bytes as the browser painted them
+    smr_ctx *ctx = nullptr;           // the lane's context (what made the frame)
+    bool have = false;
+    uint64_t gen = 0;                 // the paint it holds
+};
+struct WebInstance {
+    uint32_t w = 0, h = 0, embedding = SMR_WEB_CHROMIUM_EMBEDDING;
+    std::vector<WebStaging> staging;
+    int latest = -1;                  // the staging buffer of the latest paint; -1 until the first
+    uint64_t gen = 0;                 // paints so far
+    std::vector<smr_web_rect> rects;
+    std::deque<WebLanePage> lanes;    // one per renderer lane, grown on demand
+};
 
 struct ImageRes {
     smr_surface *surface = nullptr;  // premultiplied RGBA8 node texture at the image's own resolution (a static image; null for an animated one)
@@ -147,6 +183,9 @@ struct smr_renderer {
     std::string err;
     std::vector<smr_layout> layouts;  // scratch
     uint64_t image_launches = 0;      // smr_renderer_image_launches
+    std::map<std::string, WebInstance> web;   // smr_renderer_register_web_renderer
+    uint64_t web_launches = 0;        // smr_renderer_web_launches
+    size_t lane = 0;                  // the lane of the frame being rendered (index into lane_ctx)
 };
 
 namespace {
@@ -234,6 +273,59 @@ int ensure_surface(smr_renderer *r, smr_surface *&slot, uint32_t w, uint32_t h, 
     if (slot) { smr_surface_destroy(r->ctx, slot); slot = nullptr; }
     if (created) *created = true;
     return gpu(r, smr_surface_create(r->ctx, w, h, SMR_PX_RGBA8, &slot), "node surface");
+}
+
+// ---- web renderer instances
+// (callers have synchronised every context: sync_lanes)
+void free_web_instance(smr_renderer *r, WebInstance &wi) {
+    for (WebLanePage &lp : wi.lanes)
+        if (lp.have) smr_frame_destroy(lp.ctx, &lp.page);
+    wi.lanes.clear();
+    for (WebStaging &s : wi.staging) {
+        if (s.pinned) smr_host_free(r->lane_ctx[0], s.host);
+        else free(s.host);
+    }
+    wi.staging.clear();
+    wi.latest = -1;
+}
+// A staging buffer no upload can still be reading: the latest one again where it is idle (a host that waits for every frame keeps one
+// buffer), another idle one, a new one (up to four), and only then a wait for the oldest upload.
+int web_staging_for_paint(smr_renderer *r, WebInstance &wi) {
+    for (WebStaging &s : wi.staging) {
+        auto &f = s.in_flight;
+        for (size_t i = 0; i < f.size();)
+            if (!smr_ctx_stream_idle || smr_ctx_stream_idle(f[i]) > 0) f.erase(f.begin() + (ptrdiff_t)i);
+            else i++;
+    }
+    if (wi.latest >= 0 && wi.staging[wi.latest].in_flight.empty()) return wi.latest;
+    for (size_t i = 0; i < wi.staging.size(); i++)
+        if (wi.staging[i].in_flight.empty()) return (int)i;
+    if (wi.staging.size() < 4) {
+        WebStaging s;
+        const size_t bytes = (size_t)wi.w * 4 * wi.h;
+        if (smr_host_alloc && smr_host_free) {
+            const int rc = gpu(r, smr_host_alloc(r->lane_ctx[0], bytes, &s.host), "web page staging");
+            if (rc < 0) return rc;
+            s.pinned = true;
+        } else {
+            s.host = malloc(bytes);
+            if (!s.host) return fail(r, -2, "web page staging: out of memory");
+        }
+        wi.staging.push_back(s);
+        return (int)wi.staging.size() - 1;
+    }
+    const int k = (wi.latest + 1) % (int)wi.staging.size();  // (the one painted longest ago)
+    for (smr_ctx *c : wi.staging[k].in_flight) (void)smr_sync(c);
+    wi.staging[k].in_flight.clear();
+    return k;
+}
+bool web_instance_in_use(const smr_renderer *r, const std::string &instance_id, const std::string *except_output = nullptr) {
+    for (const auto &kv : r->outputs) {
+        if (except_output && kv.first == *except_output) continue;
+        for (const GraphNode &g : kv.second.scene.nodes())
+            if (g.kind == Kind::WebView && g.component->ref_id == instance_id) return true;
+    }
+    return false;
 }
 
 // ---- sharded renderers
@@ -473,6 +565,63 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
         int rc = render_node(r, o, g.children[k], fs, kids[k]);
         if (rc < 0) return rc;
     }
+    if (g.kind == Kind::WebView) {
+        // WebRenderer::render (web_renderer/renderer.rs:78-134): without a paint yet the node has no texture; with one, the lane's copy of the
+        // page is brought up to the latest paint and the page and the children that have a rectangle are drawn in ONE smr_web_view call
+        auto it = r->web.find(c.ref_id);
+        if (it == r->web.end()) return fail(r, -1, "Instance of web renderer \"" + c.ref_id + "\" does not exist. You have to register it first before using it in the scene definition.");
+        WebInstance &wi = it->second;
+        if (wi.latest < 0) return 0;
+        int rc = ensure_surface(r, o.l->node_surface[idx], wi.w, wi.h);
+        if (rc < 0) return rc;
+        if (wi.lanes.size() <= r->lane) wi.lanes.resize(r->lane + 1);
+        WebLanePage &lp = wi.lanes[r->lane];
+        if (!lp.have) {
+            rc = gpu(r, smr_frame_create(r->ctx, SMR_FRAME_BGRA, wi.w, wi.h, &lp.page), "web page");
+            if (rc < 0) return rc;
+            lp.have = true; lp.ctx = r->ctx; lp.gen = 0;
+        }
+        if (lp.gen != wi.gen) {
+            WebStaging &st = wi.staging[wi.latest];
+            if (smr_frame_upload_async) {
+                const void *planes[3] = {st.host, nullptr, nullptr};
+                rc = gpu(r, smr_frame_upload_async(r->ctx, &lp.page, planes), "web page upload");
+                if (rc < 0) return rc;
+                bool known = false;
+                for (smr_ctx *q : st.in_flight) known = known || q == r->ctx;
+                if (!known) st.in_flight.push_back(r->ctx);
+            }
+            lp.gen = wi.gen;
+        }
+        // children zipped with the rectangles (renderer.rs:105-114); Chromium embedding draws the page alone (:128-130)
+        const size_t n = wi.embedding == SMR_WEB_CHROMIUM_EMBEDDING ? 0 : std::min(kids.size(), wi.rects.size());
+        std::vector<const smr_surface *> srcs(n, nullptr);
+        for (size_t k = 0; k < n; k++) {
+            if (kids[k].kind == SMR_SOURCE_FRAME) {  // (a Shader node's rule: InputTexture::convert_to_node_texture)
+                rc = localize_frame(r, o, kids[k]);
+                if (rc < 0) return rc;
+                smr_surface *&t = o.l->node_surface[g.children[k]];
+                rc = ensure_surface(r, t, kids[k].w, kids[k].h);
+                if (rc < 0) return rc;
+                rc = gpu(r, smr_frame_to_rgba(r->ctx, kids[k].frame, t), "input node texture");
+                if (rc < 0) return rc;
+                srcs[k] = t;
+            } else if (kids[k].kind == SMR_SOURCE_SURFACE) {
+                srcs[k] = kids[k].surface;
+            }  // (no texture: the 1 x 1 transparent one — no pixel of the rectangle changes)
+        }
+        if (smr_web_view) {
+            smr_surface_info pi;
+            if (smr_surface_info_get(lp.page.planes[0], &pi) != 0) return fail(r, -3, "web page: the lane's copy has no plane");
+            rc = gpu(r, smr_web_view(r->ctx, pi.dptr, pi.pitch, o.l->node_surface[idx], srcs.data(), wi.rects.data(), (uint32_t)n,
+                                     wi.embedding == SMR_WEB_NATIVE_UNDER_CONTENT ? 1 : 0),
+                     "web view node");
+            if (rc < 0) return rc;
+        }
+        r->web_launches += n ? (n + 15) / 16 : 1;
+        out.kind = SMR_SOURCE_SURFACE; out.surface = o.l->node_surface[idx]; out.w = wi.w; out.h = wi.h;  // (never known to be opaque)
+        return 0;
+    }
     if (g.kind == Kind::Shader) {
         auto it = r->shaders.find(c.ref_id);
         if (it == r->shaders.end()) return fail(r, -1, "Shader \"" + c.ref_id + "\" does not exist. You have to register it first before using it in the scene definition.");
@@ -679,6 +828,7 @@ SMR_API void smr_renderer_destroy(smr_renderer *r) {
         if (kv.second.surface) smr_surface_destroy(r->ctx, kv.second.surface);
         for (smr_surface *f : kv.second.frames) smr_surface_destroy(r->ctx, f);
     }
+    for (auto &kv : r->web) free_web_instance(r, kv.second);  // (paints nobody rendered included)
     if (r->comm) smr_comm_destroy(r->comm);
     for (auto &kv : r->shaders)
         if (kv.second.hook.release) kv.second.hook.release(kv.second.hook.user);
@@ -780,6 +930,65 @@ SMR_API int smr_renderer_image_launches(const smr_renderer *r, uint64_t *count) 
     return 0;
 }
 
+// WebRenderer::new (web_renderer/renderer.rs:43-76) without the browser: the spec's resolution and embedding method
+SMR_API int smr_renderer_register_web_renderer(smr_renderer *r, const char *instance_id, uint32_t width, uint32_t height, uint32_t embedding) {
+    if (!r || !instance_id) return fail(r, -1, "smr_renderer_register_web_renderer: null argument");
+    if (!width || !height) return fail(r, -1, "smr_renderer_register_web_renderer: a web renderer's resolution cannot be zero");
+    if (width > MAX_NODE_W || height > MAX_NODE_H) return fail(r, -1, "smr_renderer_register_web_renderer: the resolution is above 7682 x 4320 (MAX_NODE_RESOLUTION)");
+    if (embedding > SMR_WEB_NATIVE_UNDER_CONTENT) return fail(r, -1, "smr_renderer_register_web_renderer: unknown embedding method");
+    if (r->web.count(instance_id)) return fail(r, -1, std::string("Failed to register a web renderer instance. Instance \"") + instance_id + "\" is already registered.");
+    WebInstance &wi = r->web[instance_id];
+    wi.w = width; wi.h = height; wi.embedding = embedding;
+    for (auto &kv : r->outputs) kv.second.scene.register_web_renderer(instance_id, (float)width, (float)height);
+    return 0;
+}
+
+SMR_API int smr_renderer_unregister_web_renderer(smr_renderer *r, const char *instance_id) {
+    if (!r || !instance_id) return fail(r, -1, "smr_renderer_unregister_web_renderer: null argument");
+    auto it = r->web.find(instance_id);
+    if (it == r->web.end()) return 0;
+    if (web_instance_in_use(r, instance_id)) return fail(r, -1, std::string("smr_renderer_unregister_web_renderer: a scene uses the web renderer instance \"") + instance_id + "\"");
+    sync_lanes(r);  // frames in flight may still read the lanes' pages, uploads the staging
+    free_web_instance(r, it->second);
+    r->web.erase(it);
+    for (auto &kv : r->outputs) kv.second.scene.unregister_web_renderer(instance_id);
+    return 0;
+}
+
+// RenderHandler::on_paint (browser_client.rs:111-130): the bitmap is copied here, uploaded by each lane when it next renders the node
+SMR_API int smr_renderer_web_paint(smr_renderer *r, const char *instance_id, const uint8_t *bgra, size_t pitch_bytes) {
+    if (!r || !instance_id || !bgra) return fail(r, -1, "smr_renderer_web_paint: null argument");
+    auto it = r->web.find(instance_id);
+    if (it == r->web.end()) return fail(r, -1, std::string("smr_renderer_web_paint: web renderer instance \"") + instance_id + "\" is not registered");
+    WebInstance &wi = it->second;
+    const size_t row = (size_t)wi.w * 4;
+    if (pitch_bytes == 0) pitch_bytes = row;
+    if (pitch_bytes < row) return fail(r, -1, "smr_renderer_web_paint: the pitch is below 4 * width");
+    const int k = web_staging_for_paint(r, wi);
+    if (k < 0) return k;
+    uint8_t *dst = (uint8_t *)wi.staging[k].host;
+    if (pitch_bytes == row) memcpy(dst, bgra, row * wi.h);
+    else for (uint32_t y = 0; y < wi.h; y++) memcpy(dst + row * y, bgra + pitch_bytes * y, row);
+    wi.latest = k;
+    wi.gen++;
+    return 0;
+}
+
+// BrowserClient's GET_FRAME_POSITIONS reply (browser_client.rs:60-93): source_transforms, one rectangle per child
+SMR_API int smr_renderer_web_positions(smr_renderer *r, const char *instance_id, const smr_web_rect *rects, uint32_t n) {
+    if (!r || !instance_id || (n && !rects)) return fail(r, -1, "smr_renderer_web_positions: null argument");
+    auto it = r->web.find(instance_id);
+    if (it == r->web.end()) return fail(r, -1, std::string("smr_renderer_web_positions: web renderer instance \"") + instance_id + "\" is not registered");
+    it->second.rects.assign(rects, rects + n);
+    return 0;
+}
+
+SMR_API int smr_renderer_web_launches(const smr_renderer *r, uint64_t *count) {
+    if (!r || !count) return -1;
+    *count = r->web_launches;
+    return 0;
+}
+
 SMR_API int smr_renderer_set_text_measurer(smr_renderer *r, smr_text_measure_fn fn, void *user) {
     if (!r) return -1;
     r->measure = fn;
@@ -856,6 +1065,7 @@ SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, ui
         return fail(r, -1, "smr_renderer_update_scene: output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12 or RGBA");
     Output &o = r->outputs[output_id];
     for (auto &kv : r->images) o.scene.register_image(kv.first, (float)kv.second.w, (float)kv.second.h);
+    for (auto &kv : r->web) o.scene.register_web_renderer(kv.first, (float)kv.second.w, (float)kv.second.h);
     o.scene.set_text_measurer(r->measure, r->measure_user);
     std::string err;
     {
@@ -870,7 +1080,24 @@ SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, ui
         Json tree;
         JsonParser jp(converted);
         std::string missing, text_err;
-        if (jp.parse(tree, err)) {
+        const bool have_tree = jp.parse(tree, err);
+        if (have_tree) {
+            // validate_web_renderer_ids_uniqueness (scene/validation.rs:74-99) over the scenes of ALL outputs with this one replaced: a web
+            // renderer instance serves one component at a time.  It runs before the stateful tree is built (state.rs:177-189), so before
+            // the lookups below.
+            std::vector<std::string> web;
+            std::string twice;
+            collect_web_instances(tree, web);
+            const std::string this_output = output_id;
+            if (!first_repeated(web, twice))
+                for (const std::string &id : web)
+                    if (twice.empty() && web_instance_in_use(r, id, &this_output)) twice = id;
+            if (!twice.empty()) {
+                if (o.w == 0) r->outputs.erase(output_id);
+                return fail(r, -1, web_renderer_not_exclusive(twice));
+            }
+        }
+        if (have_tree) {
             std::vector<const Json *> stack{&tree};
             while (!stack.empty() && missing.empty() && text_err.empty()) {
                 const Json *j = stack.back();
@@ -952,7 +1179,7 @@ SMR_API int smr_renderer_node_info(smr_renderer *r, const char *output_id, int n
     const Stateful &c = *g.component;
     memset(out, 0, sizeof(*out));
     out->kind = g.kind == Kind::InputStream ? SMR_NODE_INPUT_STREAM : g.kind == Kind::Text ? SMR_NODE_TEXT : g.kind == Kind::Image ? SMR_NODE_IMAGE
-              : g.kind == Kind::Shader ? SMR_NODE_SHADER : SMR_NODE_LAYOUT;
+              : g.kind == Kind::Shader ? SMR_NODE_SHADER : g.kind == Kind::WebView ? SMR_NODE_WEB_VIEW : SMR_NODE_LAYOUT;
     out->parent = g.parent;
     out->n_children = (uint32_t)g.children.size();
     const Size sz = g.has_forced_size ? g.forced_size : c.leaf_size;
@@ -982,6 +1209,7 @@ SMR_API int smr_renderer_render(smr_renderer *r, int64_t pts_ns, const smr_input
     const size_t lane = (size_t)(r->frame_no++ % r->lane_ctx.size());
     smr_ctx *base = r->ctx;
     r->ctx = r->lane_ctx[lane];
+    r->lane = lane;
     uint32_t k = 0;
     int rc = 0;
     for (auto &kv : r->outputs) {

@@ -72,7 +72,7 @@ struct TransitionState {
                                                bool props_changed, bool interrupt_previous, int64_t last_pts_ns);
 };
 
-enum class Kind { InputStream, View, Rescaler, Tiles, Text, Image, Shader };
+enum class Kind { InputStream, View, Rescaler, Tiles, Text, Image, Shader, WebView };
 enum class HAlign { Left, Right, Justified, Center };
 enum class VAlign { Top, Center, Bottom, Justified };
 
@@ -126,8 +126,8 @@ struct Stateful {
     Kind kind = Kind::View;
     std::string id; bool has_id = false;
     // leaves
-    std::string ref_id;          // input_id / image_id / shader_id
-    Size leaf_size;              // InputStream: filled by update_state; Text/Image/Shader: intrinsic
+    std::string ref_id;          // input_id / image_id / shader_id / (WebView) instance_id
+    Size leaf_size;              // InputStream: filled by update_state; Text/Image/Shader: intrinsic; WebView: the instance's resolution
     std::string text;            // Text payload (passed through to the caller)
     struct TextSpec {            // TextComponent as TextRendererCtx::layout_text / TextRendererNode take it (text_renderer.rs:174-233, 282-346)
         float font_size = 0, line_height = 0;
@@ -232,7 +232,7 @@ struct NestedLayout {
 
 // Render-graph node (scene_state.rs IntermediateNode / Node): layout and shader nodes are internal, the rest leaves.
 struct GraphNode {
-    Kind kind;               // View/Rescaler/Tiles => layout node; Shader; InputStream; Text; Image
+    Kind kind;               // View/Rescaler/Tiles => layout node; Shader; WebView; InputStream; Text; Image
     Stateful *component;     // layout root / leaf component (owned by the scene tree)
     int parent = -1;
     std::vector<int> children;
@@ -256,6 +256,9 @@ class Scene {
     // validates and returns the converted component tree as canonical JSON; the active scene is untouched.
     bool parse(const std::string &json, std::string &out, std::string &err) const;
     void register_image(const std::string &image_id, float w, float h) { images_[image_id] = Size{w, h}; }
+    // Renderer::register_renderer(WebRenderer) as far as the scene goes: the instance's resolution is the WebView node's size
+    void register_web_renderer(const std::string &instance_id, float w, float h) { web_renderers_[instance_id] = Size{w, h}; }
+    void unregister_web_renderer(const std::string &instance_id) { web_renderers_.erase(instance_id); }
     // the caller's text shaper (include/smr.h smr_text_measure_fn): sizes Text nodes without explicit width / height
     void set_text_measurer(smr_text_measure_fn fn, void *user) { measure_ = fn; measure_user_ = user; }
     const std::vector<GraphNode> &nodes() const { return nodes_; }
@@ -270,6 +273,7 @@ class Scene {
     std::unique_ptr<Stateful> root_;
     std::vector<GraphNode> nodes_;
     std::map<std::string, Size> images_;
+    std::map<std::string, Size> web_renderers_;
     smr_text_measure_fn measure_ = nullptr;
     void *measure_user_ = nullptr;
     std::map<std::string, Size> input_resolutions_;  // SceneState::input_resolutions — from the last render
@@ -280,6 +284,11 @@ class Scene {
 // AnimatedAsset::render's frame choice (transformations/image/animated_image.rs:120-149), exact integers: the frame whose start is closest to
 // (pts - start_pts, clamped at 0) mod (sum of the delays, 1 ns if that is 0), the first one on a tie, no wrap-around.  -1 without frames.
 int animated_frame_index(const uint64_t *delays_ns, uint32_t n_frames, int64_t pts_ns, int64_t start_pts_ns);
+// validate_web_renderer_ids_uniqueness (scene/validation.rs:74-99): the instances a scene definition or a converted tree uses, in pre-order;
+// the first id that occurs twice; SceneError::WebRendererUsageNotExclusive's text
+void collect_web_instances(const Json &component, std::vector<std::string> &out);
+bool first_repeated(const std::vector<std::string> &ids, std::string &which);
+std::string web_renderer_not_exclusive(const std::string &instance_id);
 void convert_to_shader_color(RGBA c, bool srgb, float out[4]);  // wgpu/utils.rs:51-81
 bool parse_color(const std::string &s, RGBA &out, std::string &err);  // smelter-api/src/video/color.rs
 

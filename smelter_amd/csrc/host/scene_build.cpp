@@ -102,6 +102,7 @@ struct BuildCtx {
     int64_t last_pts = 0;
     const std::map<std::string, Size> *input_resolutions = nullptr;
     const std::map<std::string, Size> *images = nullptr;
+    const std::map<std::string, Size> *web_renderers = nullptr;
     std::set<std::string> ids;  // validate_component_ids_uniqueness
     bool api_only = false;      // stop after the smelter-api conversion (TryFrom<Component>): no renderer registry, no shaper
     smr_text_measure_fn measure = nullptr;  // the caller's text shaper
@@ -625,13 +626,24 @@ std::unique_ptr<Stateful> build(const Json &j, BuildCtx &c) {
             .set("size", Json::array({Json::number(s->leaf_size.width), Json::number(s->leaf_size.height)})).set("children", jchildren(s->children));
         return s;
     }
-    if (t == "web_view") {  // parsed for API parity; there is no browser to render it (out of scope)
+    if (t == "web_view") {  // web_view_component.rs:41-71; the browser is the caller's, the node's compositing is ours
         std::string instance;
         if (!check_fields(j, "WebView", {"id", "children", "instance_id"}, c) || !get_str(j, "instance_id", instance, present, c)) return nullptr;
         if (!present) { fail(c, "missing field `instance_id`"); return nullptr; }
-        if (!c.api_only) { fail(c, "Instance of web renderer \"" + instance + "\" does not exist. You have to register it first before using it in the scene definition."); return nullptr; }
-        s->kind = Kind::Shader;
+        s->kind = Kind::WebView;
+        s->ref_id = instance;
+        if (!c.api_only) {
+            auto it = c.web_renderers ? c.web_renderers->find(instance) : std::map<std::string, Size>::const_iterator();
+            if (!c.web_renderers || it == c.web_renderers->end()) {
+                fail(c, "Instance of web renderer \"" + instance + "\" does not exist. You have to register it first before using it in the scene definition.");
+                return nullptr;
+            }
+            s->leaf_size = it->second;  // StatefulWebViewComponent::size: the instance's resolution
+        }
         if (!build_children(j, s->children, c)) return nullptr;
+        if (!c.api_only)
+            for (auto &k : s->children)
+                if (!k->has_id) { fail(c, "WebView using \"" + instance + "\" web renderer has children without \"id\" property"); return nullptr; }
         s->desc = Json::object();
         s->desc.set("type", Json::string("WebView")).set("id", jid(*s)).set("children", jchildren(s->children)).set("instance_id", Json::string(instance));
         return s;
@@ -682,7 +694,7 @@ bool build_graph(std::vector<GraphNode> &nodes, Stateful *c, int parent, const s
         c->node_children(kids);
         for (Stateful *k : kids)
             if (!build_graph(nodes, k, idx, std::nullopt, pts, err)) return false;
-    } else if (c->kind == Kind::Shader) {
+    } else if (c->kind == Kind::Shader || c->kind == Kind::WebView) {
         for (auto &k : c->children)
             if (!build_graph(nodes, k.get(), idx, std::nullopt, pts, err)) return false;
     }
@@ -690,17 +702,50 @@ bool build_graph(std::vector<GraphNode> &nodes, Stateful *c, int parent, const s
 }
 }  // namespace
 
+// The web renderer instances a component tree uses, in pre-order — of a scene definition (`"type": "web_view"`) or of a converted tree
+// (`"type": "WebView"`, Scene::parse): validate_web_renderer_ids_uniqueness visits them so (scene/validation.rs:74-99).
+void collect_web_instances(const Json &component, std::vector<std::string> &out) {
+    if (component.kind != Json::Object) return;
+    const Json *type = component.get("type"), *inst = component.get("instance_id");
+    if (type && inst && inst->kind == Json::String && (type->str == "web_view" || type->str == "WebView")) out.push_back(inst->str);
+    if (const Json *ch = component.get("children"))
+        for (const Json &k : ch->arr) collect_web_instances(k, out);
+    if (const Json *ch = component.get("child")) collect_web_instances(*ch, out);
+}
+bool first_repeated(const std::vector<std::string> &ids, std::string &which) {
+    std::set<std::string> seen;
+    for (const std::string &id : ids)
+        if (!seen.insert(id).second) { which = id; return true; }
+    return false;
+}
+std::string web_renderer_not_exclusive(const std::string &instance_id) {  // SceneError::WebRendererUsageNotExclusive (scene.rs:213-216)
+    return "Instance of web renderer \"" + instance_id + "\" was used more than once. Only one component can use specific web renderer at the time.";
+}
+
 // ------------------------------------------------------------------------------------------------ Scene
 bool Scene::update(const std::string &json, uint32_t out_w, uint32_t out_h, std::string &err) {
     Json j;
     JsonParser parser(json);
     if (!parser.parse(j, err)) return false;
+    {
+        // validate_scene_update runs on the converted scene, before the stateful tree is built (state.rs:177-189): a definition that uses
+        // web views is converted on its own first, so that its conversion errors still come before this one
+        std::vector<std::string> web;
+        collect_web_instances(j, web);
+        std::string twice, converted;
+        if (first_repeated(web, twice)) {
+            if (!parse(json, converted, err)) return false;
+            err = web_renderer_not_exclusive(twice);
+            return false;
+        }
+    }
     if (root_) recalculate_layout(*root_, Size{(float)out_w_, (float)out_h_}, last_pts_ns_, false);
     BuildCtx ctx;
     if (root_) gather_ids(*root_, ctx.prev);
     ctx.last_pts = last_pts_ns_;
     ctx.input_resolutions = &input_resolutions_;
     ctx.images = &images_;
+    ctx.web_renderers = &web_renderers_;
     ctx.measure = measure_;
     ctx.measure_user = measure_user_;
     std::unique_ptr<Stateful> root = build(j, ctx);

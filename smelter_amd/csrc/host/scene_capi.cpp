@@ -32,6 +32,12 @@ SMR_API int smr_scene_register_image(smr_scene *scene, const char *image_id, uin
     return 0;
 }
 
+SMR_API int smr_scene_register_web_renderer(smr_scene *scene, const char *instance_id, uint32_t width, uint32_t height) {
+    if (!scene || !instance_id) return set_err(scene, "smr_scene_register_web_renderer: null argument");
+    scene->scene.register_web_renderer(instance_id, (float)width, (float)height);
+    return 0;
+}
+
 SMR_API int smr_scene_set_text_measurer(smr_scene *scene, smr_text_measure_fn fn, void *user) {
     if (!scene) return -1;
     scene->scene.set_text_measurer(fn, user);
@@ -68,6 +74,7 @@ SMR_API int smr_scene_node_info(const smr_scene *scene_c, int node, smr_scene_no
     case Kind::Text: out->kind = SMR_NODE_TEXT; break;
     case Kind::Image: out->kind = SMR_NODE_IMAGE; break;
     case Kind::Shader: out->kind = SMR_NODE_SHADER; break;
+    case Kind::WebView: out->kind = SMR_NODE_WEB_VIEW; break;
     default: out->kind = SMR_NODE_LAYOUT; break;
     }
     out->parent = g.parent;

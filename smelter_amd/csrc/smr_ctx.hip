@@ -314,6 +314,20 @@ int smr_profile_read(smr_ctx *ctx, int stage, float *total_ms, uint32_t *launche
 // the HIP device of a context: for the renderer (host/renderer.cpp, smr_renderer_add_shard), not part of the ABI
 int smr_ctx_device_index(const smr_ctx *ctx) { return ctx ? ctx->device : -1; }
 
+// 1 when everything queued on the context's stream so far is done, 0 when not, < 0 on an error; never waits.  For the renderer's web page
+// staging (host/renderer.cpp: may a pinned buffer an upload was queued from be written again?), not part of the ABI
+int smr_ctx_stream_idle(smr_ctx *ctx) {
+    SMR_ENTER(ctx);
+    if (!ctx) return SMR_ERR_INVALID;
+    const hipError_t e = hipStreamQuery(ctx->stream);
+    if (e == hipSuccess) return 1;
+    if (e == hipErrorNotReady) {
+        (void)hipGetLastError();  // ("not ready" is an answer, not a failure: it must not be what the next launch's hipGetLastError finds)
+        return 0;
+    }
+    return smr_check_hip(ctx, e, "hipStreamQuery");
+}
+
 // how many layouts of a list of n this context draws (smr_render_layouts / smr_pack_layouts skip the rest, params.rs:176-182): for the
 // renderer's claims about what a layout node leaves behind (host/renderer.cpp), not part of the ABI
 uint32_t smr_ctx_drawn_layouts(const smr_ctx *ctx, uint32_t n) {

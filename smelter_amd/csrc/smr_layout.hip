@@ -12,6 +12,7 @@
 // store would quantise it, so results are identical to N separate draws while the
 // target is written once and never read.
 #include "smr_layout_dev.h"
+#include "smr_web_view.h"
 
 #include <algorithm>
 
@@ -186,6 +187,43 @@ extern "C" int smr_apply_layouts(smr_ctx *ctx, smr_surface *target, const smr_la
     rc = smr_launch_apply_layouts(ctx, target, &packed);
     if (rc != SMR_OK) return rc;
     return smr_pack_done(ctx, &packed);
+}
+
+// A WebView node's layers in one launch per 16 children (k_web_view, smr_web_view.h) — the renderer's WebView nodes (host/renderer.cpp; not
+// part of smr.h): the page, `dst`'s width x height premultiplied BGRA8 texels in device memory with rows page_pitch bytes apart, and n
+// children (a null one is the 1 x 1 transparent texture: it has no pixels) on their rectangles, blended in the order `under` gives —
+// 0: page, then children; 1: children, then the page.  No kernel counter slot: smr_renderer_web_launches counts.
+extern "C" __attribute__((visibility("default"))) int smr_web_view(smr_ctx *ctx, const void *page, size_t page_pitch, smr_surface *dst,
+                                                                   const smr_surface *const *srcs, const smr_web_rect *rects, uint32_t n, int under) {
+    SMR_ENTER(ctx);
+    if (!ctx || !page || !dst || !dst->ptr || !dst->w || !dst->h || (n && (!srcs || !rects))) return SMR_ERR_INVALID;
+    if (dst->fmt != SMR_PX_RGBA8) return smr_fail(ctx, SMR_ERR_INVALID, "smr_web_view: the target must be RGBA8");
+    if (page_pitch < (size_t)dst->w * 4 || page_pitch > 0xffffffffu || ((page_pitch | (uintptr_t)page) & 3u))
+        return smr_fail(ctx, SMR_ERR_INVALID, "smr_web_view: the page's rows are %zu bytes apart, its texels need %zu (and dword alignment)", page_pitch, (size_t)dst->w * 4);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!srcs[i]) continue;
+        if (srcs[i]->fmt != SMR_PX_RGBA8 || !srcs[i]->ptr) return smr_fail(ctx, SMR_ERR_INVALID, "smr_web_view: child %u is not an RGBA8 surface", i);
+        if (srcs[i] == dst) return smr_fail(ctx, SMR_ERR_INVALID, "smr_web_view: child %u is the target itself", i);
+    }
+    StageScope scope(ctx, SMR_STAGE_LAYOUT);
+    for (uint32_t k = 0; k < wv_launches(n); k++) {
+        WebJob J;
+        memset(&J, 0, sizeof(J));
+        J.dst = view_of(dst);
+        J.page.ptr = (u8 *)page; J.page.pitch = (u32)page_pitch; J.page.w = J.dst.w; J.page.h = J.dst.h;
+        J.pxi = ctx->srgb() ? PXI_RGBA8_SRGB : PXI_RGBA8_UNORM;
+        const uint32_t at = k * SMR_WEB_MAX_LAYERS;
+        wv_launch_set(J, k, n, under);
+        for (u32 i = 0; i < J.n; i++) {
+            if (srcs[at + i]) J.l[i].src = view_of(srcs[at + i]);
+            wv_layer_set(J.l[i], rects[at + i].x, rects[at + i].y, rects[at + i].width, rects[at + i].height, J.dst.w, J.dst.h);
+        }
+        if (!wv_plan(J)) continue;
+        dim3 grid(((u32)J.dst.w + SMR_WEB_TILE_W - 1) / SMR_WEB_TILE_W, ((u32)J.dst.h + SMR_WEB_TILE_H - 1) / SMR_WEB_TILE_H, 1);
+        hipLaunchKernelGGL(k_web_view, grid, dim3(SMR_WEB_BLOCK), 0, ctx->stream, J, ctx->d_tables);
+        SMR_HIP(ctx, hipGetLastError());
+    }
+    return SMR_OK;
 }
 
 int smr_launch_apply_layouts(smr_ctx *ctx, smr_surface *target, const PackedLayouts *p) {

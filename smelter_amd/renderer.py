@@ -114,6 +114,36 @@ class Renderer:
         self._check(self.lib.smr_renderer_image_launches(self._h, C.byref(n)))
         return n.value
 
+    # -- WebView nodes: the browser is the caller's, the node's compositing is the library's (include/smr.h, "WebView nodes")
+    def register_web_renderer(self, instance_id: str, width: int, height: int, embedding: int = _ffi.WEB_NATIVE_OVER_CONTENT):
+        """A web renderer instance of width x height; `embedding`: _ffi.WEB_CHROMIUM_EMBEDDING / WEB_NATIVE_OVER_CONTENT /
+        WEB_NATIVE_UNDER_CONTENT (smr_renderer_register_web_renderer)."""
+        self._check(self.lib.smr_renderer_register_web_renderer(self._h, instance_id.encode(), int(width), int(height), int(embedding)))
+
+    def unregister_web_renderer(self, instance_id: str):
+        self._check(self.lib.smr_renderer_unregister_web_renderer(self._h, instance_id.encode()))
+
+    def web_paint(self, instance_id: str, bgra: np.ndarray):
+        """The browser's latest paint, `bgra[h, w, 4]` premultiplied BGRA8 at the instance's resolution (smr_renderer_web_paint); a view with
+        padded rows is handed over with its pitch.  Copied before the call returns."""
+        px = np.asarray(bgra)
+        if px.dtype != np.uint8 or px.ndim != 3 or px.shape[2] != 4:
+            raise ValueError("bgra must be a uint8 [h, w, 4] array")
+        if px.strides[2] != 1 or px.strides[1] != 4 or px.strides[0] < px.shape[1] * 4:
+            px = np.ascontiguousarray(px)
+        self._check(self.lib.smr_renderer_web_paint(self._h, instance_id.encode(), px.ctypes.data, px.strides[0]))
+
+    def web_positions(self, instance_id: str, rects: Sequence[Tuple[float, float, float, float]]):
+        """One (x, y, width, height) per child, in child order, in page pixels (smr_renderer_web_positions)."""
+        arr = (_ffi.WebRect * max(len(rects), 1))(*[_ffi.WebRect(*[float(v) for v in q]) for q in rects])
+        self._check(self.lib.smr_renderer_web_positions(self._h, instance_id.encode(), arr, len(rects)))
+
+    def web_launches(self) -> int:
+        """k_web_view launches so far, all lanes (smr_renderer_web_launches)."""
+        n = C.c_uint64()
+        self._check(self.lib.smr_renderer_web_launches(self._h, C.byref(n)))
+        return n.value
+
     def set_text_measurer(self, measurer):
         """The caller's text shaper for Text nodes without explicit width / height (tests.text_twin.Shaper(...).measurer)."""
         self._measurer = measurer  # keep the callback alive

@@ -60,6 +60,10 @@ class Scene:
     def register_image(self, image_id: str, width: int, height: int):
         self._check(self._lib.smr_scene_register_image(self._h, image_id.encode(), width, height))
 
+    def register_web_renderer(self, instance_id: str, width: int, height: int):
+        """With it a `web_view` of this instance builds: a node of kind _ffi.NODE_WEB_VIEW of width x height (smr_scene_register_web_renderer)."""
+        self._check(self._lib.smr_scene_register_web_renderer(self._h, instance_id.encode(), width, height))
+
     def set_text_measurer(self, measurer):
         """`measurer`: an _ffi.TEXT_MEASURE_FN (e.g. tests.text_twin.Shaper(...).measurer) or None; sizes fitted Text nodes."""
         self._measurer = measurer  # keep the callback alive

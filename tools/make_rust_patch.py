@@ -198,6 +198,8 @@ pub struct smr_scene_node {
     pub ref_id: *const c_char, pub id: *const c_char, pub payload: *const c_char,
 }
 #[repr(C)] #[derive(Clone, Copy)]
+pub struct smr_web_rect { pub x: f32, pub y: f32, pub width: f32, pub height: f32 }
+#[repr(C)] #[derive(Clone, Copy)]
 pub struct smr_input_frame { pub input_id: *const c_char, pub frame: *const smr_frame, pub pts_ns: i64 }
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct smr_output_frame { pub output_id: *const c_char, pub frame: smr_frame, pub ctx: *mut smr_ctx }
