@@ -727,6 +727,43 @@ SMR_API int smr_renderer_register_animated_image(smr_renderer *r, const char *im
  * pass runs once per output and render, before the graph walk: every Image node whose size differs from its asset's is drawn into the
  * node's resolution — animated assets at every render, static ones once per node surface — by ONE launch per 16 such nodes. */
 SMR_API int smr_renderer_image_launches(const smr_renderer *r, uint64_t *count);
+/* SVG image assets: SvgAsset (transformations/image/svg_image.rs) without the vector library.  Parsing and rasterising stay the caller's — a
+ * host that owns resvg registers the tree's size and a callback; "decoding is the caller's", as for bitmaps and the browser.  Everything
+ * after the pixmap exists is the library's: when to rasterise, at which size, the colour fix-up, caching, the node's place in the graph.
+ *   smr_renderer_register_svg_image: width / height are SvgAsset::resolution() — tree.size truncated (svg_image.rs:89-94) — and size Image
+ *     nodes exactly as a bitmap's do (scene/image_component.rs:67-89, integer aspect ratio included).  SMR_ERR_INVALID: whatever
+ *     smr_renderer_register_image refuses (null arguments, a zero size, an id that names a static, animated or SVG image already) and a
+ *     null fn.  Nothing is rasterised at registration.
+ *   fn runs only inside smr_renderer_update_scene, on the calling thread, never from smr_renderer_render: once for every (SVG asset, node
+ *     width, node height) the new scene needs and no resident raster covers — the reference rasterises at the NODE's resolution
+ *     (svg_image.rs:262-292, scale = node size / tree size), it does not rescale a bitmap —, after the definition has been validated and
+ *     before the new scene becomes active.  The buffer is pinned staging (smr_host_alloc), tight (pitch_bytes == 4 * width) and zero-filled.
+ *     A non-zero return refuses the update as a whole, like a validation error (SMR_ERR_INVALID): the previous scene stays active,
+ *     smr_renderer_last_error names the image and the size, and what was rasterised for the refused update is released.  So does a staging
+ *     or raster allocation that fails (SMR_ERR_OOM), and a node above MAX_NODE_RESOLUTION.  A node of zero width or height gets no call and
+ *     samples transparent.  fn MUST NOT call into the same renderer.
+ *   After all calls of one update every new pixmap is uploaded into an RGBA8 surface of the node's size on the renderer's own context and
+ *     fixed up in place — un-premultiplied through the linear view, quantised to 8 bits, premultiplied through the sRGB view
+ *     (svg_image.rs:120-167) — by ONE k_svg_nodes launch per 16 new rasters in SMR_MODE_GPU_OPTIMIZED, and by none in
+ *     SMR_MODE_CPU_OPTIMIZED, where the pixmap's bytes are the node's (svg_image.rs:73-76); one smr_sync follows.  A pixmap whose alpha is 255
+ *     everywhere is handed on as an opaque layer.  Rasters are keyed by (registration, width, height) and shared by all nodes, outputs and
+ *     lanes of that size; the node never goes through the image pass (smr_renderer_image_launches does not move).  A raster that no active
+ *     scene of any output shows after an update (or smr_renderer_unregister_output) is released, once frames in flight are done with it.
+ *     With shards, Image nodes render on the root, as ever.
+ *   smr_renderer_unregister_image: unregister_renderer(id, RegistryType::Image) (state.rs:154-171) for static, animated and SVG images
+ *     alike.  Refused (SMR_ERR_INVALID) while an active scene uses the id; an unknown id is not an error.  Frees the asset's surfaces and
+ *     rasters; after it returns fn is never called for that id again, and the id may be registered anew.
+ *   smr_renderer_svg_stats: calls of fn so far, k_svg_nodes launches so far, rasters resident now (no kernel counter slot, like
+ *     smr_renderer_image_launches).  Any out-pointer may be null.
+ * Out of scope: parsing or rasterising SVG in the library; re-rasterising while a parent Rescaler animates (the reference does not either:
+ * the node's size is the component's); WebGl mode. */
+/* Rasterise image `image_id` at width x height into `rgba`: premultiplied, gamma-encoded RGBA8, rows pitch_bytes apart, zero-filled by the
+ * library before the call — what render_to_texture (svg_image.rs:262-292) leaves in its BytesMut.  0 = done; anything else fails the update. */
+typedef int (*smr_svg_rasterise_fn)(void *user, const char *image_id, uint32_t width, uint32_t height, uint8_t *rgba, size_t pitch_bytes);
+SMR_API int smr_renderer_register_svg_image(smr_renderer *r, const char *image_id, uint32_t width, uint32_t height,
+                                            smr_svg_rasterise_fn fn, void *user);
+SMR_API int smr_renderer_unregister_image(smr_renderer *r, const char *image_id);
+SMR_API int smr_renderer_svg_stats(const smr_renderer *r, uint64_t *rasterise_calls, uint64_t *launches, uint32_t *resident);
 /* WebView nodes: the compositing half of the reference's web renderer (transformations/web_renderer/renderer.rs:78-134, shader.rs:53-114,
  * render_website.wgsl).  The browser is the caller's — no CEF, no process, no shared memory here: a host that
  * owns one registers an instance, hands over the latest paint and the latest rectangles of the children, and a `web_view` component of that
@@ -777,7 +814,8 @@ SMR_API int smr_renderer_register_shader(smr_renderer *r, const char *shader_id,
 SMR_API int smr_renderer_register_shader_source(smr_renderer *r, const char *shader_id, const char *hip_source);
 SMR_API int smr_renderer_register_shader_program(smr_renderer *r, const char *shader_id, const smr_shader_program *p);
 /* An update is refused as a whole — the previous scene stays active — for everything the scene definition can get wrong: validation errors,
- * unknown shader ids, and (with a font book) Text nodes no run can be made of (empty font book, text that is not UTF-8, absurd sizes).  One
+ * unknown shader ids, (with a font book) Text nodes no run can be made of (empty font book, text that is not UTF-8, absurd sizes), and an
+ * SVG asset's raster that could not be made (the rasteriser said no, or an allocation failed: "SVG image assets" above).  One
  * failure is reported AFTER the new scene is in place: a device allocation that fails while the output's frames or a Text node's surface are
  * created (SMR_ERR_OOM): the new scene is active, the nodes that could not be drawn render transparent. */
 SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, uint32_t width, uint32_t height, uint32_t output_format,
@@ -838,7 +876,9 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      smr_renderer_image_launches: no struct changed, smr_scene_node keeps its layout, no kernel counter slot was added);
  *      WebView nodes (smr_scene_register_web_renderer, smr_renderer_register_web_renderer / _unregister_web_renderer, smr_renderer_web_paint,
  *      smr_renderer_web_positions, smr_renderer_web_launches, smr_web_rect, smr_web_embedding, SMR_NODE_WEB_VIEW = 5: a node kind no
- *      version-2 scene could produce — `web_view` was refused —, no struct changed, no kernel counter slot was added).
+ *      version-2 scene could produce — `web_view` was refused —, no struct changed, no kernel counter slot was added);
+ *      SVG image assets and image unregistration (smr_svg_rasterise_fn, smr_renderer_register_svg_image, smr_renderer_unregister_image,
+ *      smr_renderer_svg_stats: no struct changed, no kernel counter slot was added, no existing scene renders differently).
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

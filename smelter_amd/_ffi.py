@@ -53,6 +53,7 @@ EXPORTS = [
     "smr_renderer_register_animated_image", "smr_animated_frame_index", "smr_scene_node_start_pts", "smr_renderer_image_launches",
     "smr_scene_register_web_renderer", "smr_renderer_register_web_renderer", "smr_renderer_unregister_web_renderer", "smr_renderer_web_paint",
     "smr_renderer_web_positions", "smr_renderer_web_launches",
+    "smr_renderer_register_svg_image", "smr_renderer_unregister_image", "smr_renderer_svg_stats",
     "smr_abi_version", "smr_build_flags", "smr_sizeof_layout",
 ]
 NO_RESOLUTION = 0xFFFFFFFF
@@ -123,6 +124,8 @@ class TextRun(C.Structure):
 
 
 TEXT_MEASURE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(TextParams), C.POINTER(C.c_float), C.POINTER(C.c_uint32))
+# smr_svg_rasterise_fn(user, image_id, width, height, rgba, pitch_bytes)
+SVG_RASTERISE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_size_t)
 
 
 class Source(C.Structure):
@@ -272,6 +275,9 @@ def load():
         "smr_renderer_web_paint": ([P, C.c_char_p, P, C.c_size_t], I),
         "smr_renderer_web_positions": ([P, C.c_char_p, C.POINTER(WebRect), U], I),
         "smr_renderer_web_launches": ([P, C.POINTER(C.c_uint64)], I),
+        "smr_renderer_register_svg_image": ([P, C.c_char_p, U, U, SVG_RASTERISE_FN, P], I),
+        "smr_renderer_unregister_image": ([P, C.c_char_p], I),
+        "smr_renderer_svg_stats": ([P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], I),
         "smr_abi_version": ([], U),
         "smr_build_flags": ([], U),
         "smr_sizeof_layout": ([], U),

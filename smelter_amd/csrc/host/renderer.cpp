@@ -43,6 +43,9 @@ extern "C" int smr_image_nodes(smr_ctx *ctx, const smr_surface *const *src, smr_
 extern "C" int smr_web_view(smr_ctx *ctx, const void *page, size_t page_pitch, smr_surface *dst, const smr_surface *const *srcs, const smr_web_rect *rects,
                             uint32_t n, int under) __attribute__((weak));
 extern "C" int smr_ctx_stream_idle(smr_ctx *ctx) __attribute__((weak));
+// The colour fix-up of new SVG rasters (k_svg_nodes, smr_convert.hip; not part of the ABI): n surfaces in place, one launch per 16.  Without
+// the GPU half the rasters keep the pixmap's bytes (nothing is drawn there either).
+extern "C" int smr_svg_nodes(smr_ctx *ctx, smr_surface *const *surfaces, uint32_t n) __attribute__((weak));
 #pragma weak smr_host_alloc
 #pragma weak smr_host_free
 #pragma weak smr_frame_upload_async
@@ -83,6 +86,17 @@ struct ImageRes {
     std::vector<uint8_t> frame_opaque;
     std::vector<uint64_t> delays_ns;
     bool animated() const { return !frames.empty(); }
+    // SvgAsset (svg_image.rs:20-118) without the vector library: the caller's rasteriser, and one node texture per node size an active scene
+    // shows the asset at — made by smr_renderer_update_scene, shared by every node, output and lane of that size, released when no active
+    // scene is left that needs it.  w / h above are SvgAsset::resolution().
+    smr_svg_rasterise_fn svg_fn = nullptr;
+    void *svg_user = nullptr;
+    struct Raster {
+        smr_surface *surface = nullptr;
+        bool opaque = false;  // every alpha byte of the pixmap was 255 (the fix-up keeps the alpha byte)
+    };
+    std::map<std::pair<uint32_t, uint32_t>, Raster> rasters;  // by (node width, node height)
+    bool svg() const { return svg_fn != nullptr; }
 };
 
 struct Source {
@@ -185,6 +199,7 @@ struct smr_renderer {
     uint64_t image_launches = 0;      // smr_renderer_image_launches
     std::map<std::string, WebInstance> web;   // smr_renderer_register_web_renderer
     uint64_t web_launches = 0;        // smr_renderer_web_launches
+    uint64_t svg_calls = 0, svg_launches = 0;  // smr_renderer_svg_stats
     size_t lane = 0;                  // the lane of the frame being rendered (index into lane_ctx)
 };
 
@@ -326,6 +341,136 @@ bool web_instance_in_use(const smr_renderer *r, const std::string &instance_id, 
             if (g.kind == Kind::WebView && g.component->ref_id == instance_id) return true;
     }
     return false;
+}
+
+// ---- SVG image assets
+bool image_in_use(const smr_renderer *r, const std::string &image_id) {
+    for (const auto &kv : r->outputs)
+        for (const GraphNode &g : kv.second.scene.nodes())
+            if (g.kind == Kind::Image && g.component->ref_id == image_id) return true;
+    return false;
+}
+// (callers have synchronised every context: sync_lanes)
+void free_image(smr_renderer *r, ImageRes &img) {
+    if (img.surface) smr_surface_destroy(r->lane_ctx[0], img.surface);
+    for (smr_surface *f : img.frames) smr_surface_destroy(r->lane_ctx[0], f);
+    for (auto &kv : img.rasters) smr_surface_destroy(r->lane_ctx[0], kv.second.surface);
+    img.surface = nullptr;
+    img.frames.clear();
+    img.rasters.clear();
+}
+// Rasters no active scene of any output shows any more.  (Callers have synchronised every context, as for the Text surfaces of a replaced
+// scene: frames in flight may still sample them.)
+void release_unused_rasters(smr_renderer *r) {
+    std::set<std::pair<std::string, std::pair<uint32_t, uint32_t>>> used;
+    for (const auto &kv : r->outputs)
+        for (const GraphNode &g : kv.second.scene.nodes())
+            if (g.kind == Kind::Image) used.insert({g.component->ref_id, {as_u32(g.component->leaf_size.width), as_u32(g.component->leaf_size.height)}});
+    for (auto &kv : r->images) {
+        auto &rasters = kv.second.rasters;
+        for (auto it = rasters.begin(); it != rasters.end();) {
+            if (used.count({kv.first, it->first})) { ++it; continue; }
+            smr_surface_destroy(r->lane_ctx[0], it->second.surface);
+            it = rasters.erase(it);
+        }
+    }
+}
+
+// One pixmap on its way to a raster: what the rasteriser filled, and the surface it is uploaded into
+struct SvgPending {
+    std::string id;
+    uint32_t w = 0, h = 0;
+    void *host = nullptr;  // w * 4 * h bytes, tight rows, zero-filled before the call
+    bool pinned = false;   // from smr_host_alloc (else plain memory: no GPU half)
+    smr_surface *surface = nullptr;
+    bool opaque = false;
+};
+void free_svg_staging(smr_renderer *r, std::vector<SvgPending> &pend) {
+    for (SvgPending &p : pend) {
+        if (p.pinned) smr_host_free(r->lane_ctx[0], p.host);
+        else free(p.host);
+        p.host = nullptr;
+    }
+}
+// The rasters a new render graph needs and no resident one covers (SvgAsset::render_to_texture at the NODE's resolution, svg_image.rs:262-292):
+// the caller's rasteriser runs once per (asset, node width, node height), every new pixmap is uploaded into a surface of the node's size,
+// the colour fix-up runs in place — one smr_svg_nodes call, i.e. one launch per 16 rasters; none in CPU-optimized mode, where the pixmap's
+// bytes are the node's (svg_image.rs:73-76) — and one smr_sync lets the staging go and every lane read.  Anything that fails leaves nothing
+// behind: 0, or the status with `err` set.
+int make_svg_rasters(smr_renderer *r, const std::vector<GraphNode> &nodes, std::string &err) {
+    std::vector<SvgPending> pend;
+    int rc = 0;
+    for (const GraphNode &g : nodes) {
+        if (g.kind != Kind::Image) continue;
+        auto it = r->images.find(g.component->ref_id);
+        if (it == r->images.end() || !it->second.svg()) continue;
+        const ImageRes &img = it->second;
+        const uint32_t w = as_u32(g.component->leaf_size.width), h = as_u32(g.component->leaf_size.height);
+        if (!w || !h || img.rasters.count({w, h})) continue;  // (a node without texels samples transparent)
+        bool queued = false;
+        for (const SvgPending &p : pend) queued = queued || (p.id == it->first && p.w == w && p.h == h);
+        if (queued) continue;
+        const std::string what = "SVG image \"" + it->first + "\" at " + std::to_string(w) + "x" + std::to_string(h);
+        if (w > MAX_NODE_W || h > MAX_NODE_H) { err = what + ": the node is above 7682 x 4320 (MAX_NODE_RESOLUTION)"; rc = -1; break; }
+        SvgPending p;
+        p.id = it->first; p.w = w; p.h = h;
+        const size_t bytes = (size_t)w * 4 * h;
+        if (smr_host_alloc && smr_host_free) {
+            rc = smr_host_alloc(r->lane_ctx[0], bytes, &p.host);
+            if (rc < 0) { err = what + ": pixmap staging: " + smr_last_error(r->lane_ctx[0]); break; }
+            p.pinned = true;
+        } else {
+            p.host = malloc(bytes);
+            if (!p.host) { err = what + ": pixmap staging: out of memory"; rc = -2; break; }
+        }
+        memset(p.host, 0, bytes);
+        pend.push_back(p);
+        r->svg_calls++;
+        const int answer = img.svg_fn(img.svg_user, p.id.c_str(), w, h, (uint8_t *)p.host, (size_t)w * 4);
+        if (answer != 0) { err = what + ": the rasteriser failed (" + std::to_string(answer) + ")"; rc = -1; break; }
+    }
+    bool queued_work = false;
+    std::vector<smr_surface *> fresh;
+    for (size_t i = 0; i < pend.size() && rc >= 0; i++) {
+        SvgPending &p = pend[i];
+        const std::string what = "SVG image \"" + p.id + "\" at " + std::to_string(p.w) + "x" + std::to_string(p.h);
+        rc = smr_surface_create(r->lane_ctx[0], p.w, p.h, SMR_PX_RGBA8, &p.surface);
+        if (rc < 0) { p.surface = nullptr; err = what + ": raster: " + smr_last_error(r->lane_ctx[0]); break; }
+        fresh.push_back(p.surface);
+        if (p.pinned && smr_frame_upload_async) {
+            smr_frame f = {};
+            f.format = SMR_FRAME_RGBA; f.width = p.w; f.height = p.h; f.planes[0] = p.surface;
+            const void *const planes[3] = {p.host, nullptr, nullptr};
+            rc = smr_frame_upload_async(r->lane_ctx[0], &f, planes);
+        } else {
+            rc = smr_surface_upload(r->lane_ctx[0], p.surface, p.host, (size_t)p.w * 4);
+        }
+        queued_work = true;
+        if (rc < 0) { err = what + ": upload: " + smr_last_error(r->lane_ctx[0]); break; }
+        const uint8_t *px = (const uint8_t *)p.host;
+        p.opaque = true;
+        for (size_t k = 0, n = (size_t)p.w * p.h; k < n && p.opaque; k++) p.opaque = px[4 * k + 3] == 255;
+    }
+    if (rc >= 0 && !fresh.empty() && smr_svg_nodes && smr_ctx_mode(r->lane_ctx[0]) == SMR_MODE_GPU_OPTIMIZED) {
+        rc = smr_svg_nodes(r->lane_ctx[0], fresh.data(), (uint32_t)fresh.size());
+        if (rc < 0) err = std::string("SVG rasters: ") + smr_last_error(r->lane_ctx[0]);
+        else r->svg_launches += (fresh.size() + 15) / 16;
+    }
+    if (queued_work) {  // (also after a failure: an upload may still read the staging, the fix-up the surfaces)
+        const int e = smr_sync(r->lane_ctx[0]);
+        if (e < 0 && rc >= 0) { rc = e; err = std::string("SVG rasters: ") + smr_last_error(r->lane_ctx[0]); }
+    }
+    free_svg_staging(r, pend);
+    if (rc < 0) {
+        for (smr_surface *s : fresh) smr_surface_destroy(r->lane_ctx[0], s);
+        return rc;
+    }
+    for (const SvgPending &p : pend) {
+        ImageRes::Raster ra;
+        ra.surface = p.surface; ra.opaque = p.opaque;
+        r->images[p.id].rasters[{p.w, p.h}] = ra;
+    }
+    return 0;
 }
 
 // ---- sharded renderers
@@ -475,7 +620,8 @@ static void flatten_shader_param(const Json &j, std::vector<uint8_t> &out) {
 // the frame of this pts on the node's own clock (AnimatedAsset::render, animated_image.rs:120-149) where the node has the asset's size;
 // otherwise the lane's surface of the node's size, into which the asset is drawn bilinearly (bitmap_image.rs:65-88) — an animated one at
 // every render, a static one only until it has been drawn into the surface the lane holds (was_rendered, bitmap_image.rs:71-73).  All the
-// drawing of the pass is ONE smr_image_nodes call: one launch per 16 nodes where there was one per node.
+// drawing of the pass is ONE smr_image_nodes call: one launch per 16 nodes where there was one per node.  An SVG asset's node takes the
+// raster smr_renderer_update_scene made for its size and is never drawn here.
 int image_pass(smr_renderer *r, Output &o, const FrameSetView &fs) {
     const std::vector<GraphNode> &nodes = o.scene.nodes();
     OutputLane &l = *o.l;
@@ -499,6 +645,12 @@ int image_pass(smr_renderer *r, Output &o, const FrameSetView &fs) {
         }
         const uint32_t w = as_u32(c.leaf_size.width), h = as_u32(c.leaf_size.height);
         Source &out = l.image_source[idx];
+        if (img.svg()) {
+            // the raster smr_renderer_update_scene made for this node size: never rescaled, never drawn here (no raster: transparent)
+            auto ra = img.rasters.find({w, h});
+            if (ra != img.rasters.end()) { out.kind = SMR_SOURCE_SURFACE; out.surface = ra->second.surface; out.w = w; out.h = h; out.opaque = ra->second.opaque; }
+            continue;
+        }
         if (w == img.w && h == img.h) {
             out.kind = SMR_SOURCE_SURFACE; out.surface = asset; out.w = w; out.h = h; out.opaque = opaque;
             continue;
@@ -824,10 +976,7 @@ SMR_API void smr_renderer_destroy(smr_renderer *r) {
     if (!r) return;
     sync_lanes(r);
     for (auto &kv : r->outputs) free_output(r, kv.second);
-    for (auto &kv : r->images) {
-        if (kv.second.surface) smr_surface_destroy(r->ctx, kv.second.surface);
-        for (smr_surface *f : kv.second.frames) smr_surface_destroy(r->ctx, f);
-    }
+    for (auto &kv : r->images) free_image(r, kv.second);  // (resident SVG rasters included)
     for (auto &kv : r->web) free_web_instance(r, kv.second);  // (paints nobody rendered included)
     if (r->comm) smr_comm_destroy(r->comm);
     for (auto &kv : r->shaders)
@@ -927,6 +1076,43 @@ SMR_API int smr_renderer_register_animated_image(smr_renderer *r, const char *im
 SMR_API int smr_renderer_image_launches(const smr_renderer *r, uint64_t *count) {
     if (!r || !count) return -1;
     *count = r->image_launches;
+    return 0;
+}
+
+// SvgAsset::new after the parser (svg_image.rs:31-94): the tree's size and the way back to the host's rasteriser.  Nothing is rasterised here.
+SMR_API int smr_renderer_register_svg_image(smr_renderer *r, const char *image_id, uint32_t width, uint32_t height, smr_svg_rasterise_fn fn, void *user) {
+    if (!r || !image_id || !fn || !width || !height) return fail(r, -1, "smr_renderer_register_svg_image: null argument");
+    if (r->images.count(image_id)) return fail(r, -1, std::string("Failed to register an image. Image \"") + image_id + "\" is already registered.");
+    ImageRes res;
+    res.w = width; res.h = height;
+    res.svg_fn = fn; res.svg_user = user;
+    r->images[image_id] = res;
+    for (auto &kv : r->outputs) kv.second.scene.register_image(image_id, (float)width, (float)height);
+    return 0;
+}
+
+// unregister_renderer(id, RegistryType::Image) (state.rs:154-171), for a static, an animated and an SVG image alike
+SMR_API int smr_renderer_unregister_image(smr_renderer *r, const char *image_id) {
+    if (!r || !image_id) return fail(r, -1, "smr_renderer_unregister_image: null argument");
+    auto it = r->images.find(image_id);
+    if (it == r->images.end()) return 0;
+    if (image_in_use(r, image_id)) return fail(r, -1, std::string("smr_renderer_unregister_image: a scene uses the image \"") + image_id + "\"");
+    sync_lanes(r);  // frames in flight may still sample a scene that was replaced a moment ago
+    free_image(r, it->second);
+    r->images.erase(it);
+    for (auto &kv : r->outputs) kv.second.scene.unregister_image(image_id);
+    return 0;
+}
+
+SMR_API int smr_renderer_svg_stats(const smr_renderer *r, uint64_t *rasterise_calls, uint64_t *launches, uint32_t *resident) {
+    if (!r) return -1;
+    if (rasterise_calls) *rasterise_calls = r->svg_calls;
+    if (launches) *launches = r->svg_launches;
+    if (resident) {
+        size_t n = 0;
+        for (const auto &kv : r->images) n += kv.second.rasters.size();
+        *resident = (uint32_t)n;
+    }
     return 0;
 }
 
@@ -1135,9 +1321,16 @@ SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, ui
             return fail(r, -1, text_err);
         }
     }
-    if (!o.scene.update(scene_json, width, height, err)) {
+    // SVG assets are rasterised at the sizes the NEW graph shows them at — on this thread, once everything about the definition has been
+    // validated and before the graph replaces the active one: a rasteriser (or a raster's allocation) that fails refuses the update as a whole.
+    int svg_rc = 0;
+    const Scene::BeforeCommit rasterise = [&](const std::vector<GraphNode> &new_nodes, std::string &why) {
+        svg_rc = make_svg_rasters(r, new_nodes, why);
+        return svg_rc >= 0;
+    };
+    if (!o.scene.update(scene_json, width, height, err, rasterise)) {
         if (o.w == 0) r->outputs.erase(output_id);  // a failed first update leaves no output behind
-        return fail(r, -1, err);
+        return fail(r, svg_rc < 0 ? svg_rc : -1, err);
     }
     // frames in flight read the surfaces dropped below
     sync_lanes(r);
@@ -1146,6 +1339,7 @@ SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, ui
     o.w = width; o.h = height; o.format = output_format;
     // node indices belong to the new graph: per-node surfaces are re-created on demand, text runs must be supplied again
     free_node_surfaces(r, o);
+    release_unused_rasters(r);  // (the replaced scene's SVG rasters, where no output shows them any more)
     int rc = enter_lane(r, o, 0);  // the output's first frames exist after a successful update, as before
     // (what is left to fail below is a device allocation — the frames, a text node's surface: SMR_ERR_OOM with the NEW scene active and the
     //  nodes that could not be drawn transparent; include/smr.h says so.  Everything the scene itself can get wrong was refused above.)
@@ -1160,6 +1354,7 @@ SMR_API int smr_renderer_unregister_output(smr_renderer *r, const char *output_i
     sync_lanes(r);
     free_output(r, it->second);
     r->outputs.erase(it);
+    release_unused_rasters(r);
     return 0;
 }
 

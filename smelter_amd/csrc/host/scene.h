@@ -5,6 +5,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <optional>
@@ -251,11 +252,15 @@ struct GraphNode {
 class Scene {
   public:
     // Renderer::update_scene (state.rs:177-189, scene/scene_state.rs:74-127)
-    bool update(const std::string &json, uint32_t out_w, uint32_t out_h, std::string &err);
+    // `before_commit` (may be empty) sees the new render graph once everything about the definition has been validated and before it replaces
+    // the active one: false (with `err` set) refuses the update like a validation error — the previous scene stays.
+    using BeforeCommit = std::function<bool(const std::vector<GraphNode> &new_nodes, std::string &err)>;
+    bool update(const std::string &json, uint32_t out_w, uint32_t out_h, std::string &err, const BeforeCommit &before_commit = BeforeCommit());
     // The smelter-api conversion alone (TryFrom<Component> for scene::Component, smelter-api/src/video/component_into.rs):
     // validates and returns the converted component tree as canonical JSON; the active scene is untouched.
     bool parse(const std::string &json, std::string &out, std::string &err) const;
     void register_image(const std::string &image_id, float w, float h) { images_[image_id] = Size{w, h}; }
+    void unregister_image(const std::string &image_id) { images_.erase(image_id); }
     // Renderer::register_renderer(WebRenderer) as far as the scene goes: the instance's resolution is the WebView node's size
     void register_web_renderer(const std::string &instance_id, float w, float h) { web_renderers_[instance_id] = Size{w, h}; }
     void unregister_web_renderer(const std::string &instance_id) { web_renderers_.erase(instance_id); }

@@ -723,7 +723,7 @@ std::string web_renderer_not_exclusive(const std::string &instance_id) {  // Sce
 }
 
 // ------------------------------------------------------------------------------------------------ Scene
-bool Scene::update(const std::string &json, uint32_t out_w, uint32_t out_h, std::string &err) {
+bool Scene::update(const std::string &json, uint32_t out_w, uint32_t out_h, std::string &err, const BeforeCommit &before_commit) {
     Json j;
     JsonParser parser(json);
     if (!parser.parse(j, err)) return false;
@@ -752,6 +752,7 @@ bool Scene::update(const std::string &json, uint32_t out_w, uint32_t out_h, std:
     if (!root) { err = ctx.err; return false; }
     std::vector<GraphNode> nodes;
     if (!build_graph(nodes, root.get(), -1, Size{(float)out_w, (float)out_h}, last_pts_ns_, err)) return false;
+    if (before_commit && !before_commit(nodes, err)) return false;
     root_ = std::move(root);
     nodes_ = std::move(nodes);
     out_w_ = out_w; out_h_ = out_h;

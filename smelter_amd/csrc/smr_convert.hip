@@ -11,6 +11,7 @@
 // on a fresh cache line.
 #include "smr_convert_dev.h"
 #include "smr_convert_420.h"
+#include "smr_svg_nodes.h"
 
 namespace {
 
@@ -793,6 +794,36 @@ int smr_frame_fill_black(smr_ctx *ctx, const smr_frame *out) {
                            row_bytes, b * 0x01010101u);
     }
     SMR_HIP(ctx, hipGetLastError());
+    return SMR_OK;
+}
+
+// smr_remove_premultiplied_alpha followed by smr_add_premultiplied_alpha through the sRGB view, in place, for n surfaces at once — the
+// renderer's SVG rasters (host/renderer.cpp; not part of smr.h): one launch of k_svg_nodes per 16 surfaces, the bytes the two passes chained
+// would write.  A CPU-optimized context has no such step (svg_image.rs:73-76: the pixmap's bytes are the node's) and calling this there is an
+// error.  No kernel counter slot: smr_renderer_svg_stats counts.
+__attribute__((visibility("default"))) int smr_svg_nodes(smr_ctx *ctx, smr_surface *const *surfaces, uint32_t n) {
+    SMR_ENTER(ctx);
+    if (!ctx || (n && !surfaces)) return SMR_ERR_INVALID;
+    if (!ctx->srgb()) return smr_fail(ctx, SMR_ERR_INVALID, "smr_svg_nodes: a CPU-optimized context keeps the pixmap's bytes");
+    for (uint32_t i = 0; i < n; i++) {
+        if (!surfaces[i] || !surfaces[i]->ptr || !surfaces[i]->w || !surfaces[i]->h) return smr_fail(ctx, SMR_ERR_INVALID, "smr_svg_nodes: entry %u lacks a surface", i);
+        if (surfaces[i]->fmt != SMR_PX_RGBA8) return smr_fail(ctx, SMR_ERR_INVALID, "smr_svg_nodes: surfaces must be RGBA8");
+        if (surfaces[i]->pitch < (size_t)surfaces[i]->w * 4 || (((uintptr_t)surfaces[i]->ptr | surfaces[i]->pitch) & 3u))
+            return smr_fail(ctx, SMR_ERR_INVALID, "smr_svg_nodes: entry %u: rows of %zu bytes for %u texels (and dword alignment)", i, surfaces[i]->pitch, surfaces[i]->w);
+        for (uint32_t k = 0; k < i; k++)
+            if (surfaces[k] == surfaces[i]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_svg_nodes: entry %u repeats entry %u (the work is in place)", i, k);
+    }
+    StageScope scope(ctx, SMR_STAGE_INGEST);
+    for (uint32_t at = 0; at < n; at += SMR_SVG_MAX_JOBS) {
+        SvgBatch B;
+        memset(&B, 0, sizeof(B));
+        B.n = n - at < SMR_SVG_MAX_JOBS ? n - at : SMR_SVG_MAX_JOBS;
+        for (u32 i = 0; i < B.n; i++) B.j[i].px = view_of(surfaces[at + i]);
+        const u32 blocks = sv_plan(B);
+        if (!blocks) continue;
+        hipLaunchKernelGGL(k_svg_nodes, dim3(blocks), dim3(SMR_SVG_BLOCK), 0, ctx->stream, B, ctx->d_tables);
+        SMR_HIP(ctx, hipGetLastError());
+    }
     return SMR_OK;
 }
 

@@ -114,6 +114,40 @@ class Renderer:
         self._check(self.lib.smr_renderer_image_launches(self._h, C.byref(n)))
         return n.value
 
+    # -- SVG image assets: the vector library is the caller's, everything after the pixmap the library's (include/smr.h, "SVG image assets")
+    def register_svg_image(self, image_id: str, width: int, height: int, rasterise):
+        """An SVG asset of intrinsic width x height (smr_renderer_register_svg_image).  `rasterise(w, h)` returns the asset drawn at w x h as
+        an (h, w, 4) uint8 array, premultiplied and gamma-encoded; it runs inside update_scene, once per node size no resident raster covers.
+        An exception refuses that update, with its text appended to the error.  It must not call into this renderer."""
+        errors = self._svg_errors = getattr(self, "_svg_errors", {})
+
+        def call(_user, _id, w, h, rgba, pitch):
+            try:
+                px = np.asarray(rasterise(int(w), int(h)))
+                if px.dtype != np.uint8 or px.shape != (h, w, 4):
+                    raise ValueError(f"rasterise({w}, {h}) returned {px.dtype} {px.shape}, not uint8 ({h}, {w}, 4)")
+                dst = np.ctypeslib.as_array(rgba, shape=(h, pitch))
+                dst[:, :w * 4] = px.reshape(h, w * 4)
+                return 0
+            except BaseException as e:  # (nothing may unwind through the C frames above)
+                errors[image_id] = f"{type(e).__name__}: {e}"
+                return 1
+        cb = _ffi.SVG_RASTERISE_FN(call)
+        self._check(self.lib.smr_renderer_register_svg_image(self._h, image_id.encode(), int(width), int(height), cb, None))
+        self._svg_callbacks = getattr(self, "_svg_callbacks", {})
+        self._svg_callbacks[image_id] = cb  # kept alive for the registration's life
+
+    def unregister_image(self, image_id: str):
+        """A static, animated or SVG image (smr_renderer_unregister_image); refused while an active scene uses it."""
+        self._check(self.lib.smr_renderer_unregister_image(self._h, image_id.encode()))
+        getattr(self, "_svg_callbacks", {}).pop(image_id, None)
+
+    def svg_stats(self) -> Tuple[int, int, int]:
+        """(calls of the rasterisers so far, k_svg_nodes launches so far, rasters resident now) (smr_renderer_svg_stats)."""
+        calls, launches, resident = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self._check(self.lib.smr_renderer_svg_stats(self._h, C.byref(calls), C.byref(launches), C.byref(resident)))
+        return calls.value, launches.value, resident.value
+
     # -- WebView nodes: the browser is the caller's, the node's compositing is the library's (include/smr.h, "WebView nodes")
     def register_web_renderer(self, instance_id: str, width: int, height: int, embedding: int = _ffi.WEB_NATIVE_OVER_CONTENT):
         """A web renderer instance of width x height; `embedding`: _ffi.WEB_CHROMIUM_EMBEDDING / WEB_NATIVE_OVER_CONTENT /
@@ -170,7 +204,12 @@ class Renderer:
     # -- scenes (state.rs:177-189)
     def update_scene(self, output_id: str, width: int, height: int, scene: Union[str, dict], output_format: int = FRAME_PLANAR_YUV420) -> List[Node]:
         text = scene if isinstance(scene, str) else json.dumps(scene)
-        self._check(self.lib.smr_renderer_update_scene(self._h, output_id.encode(), width, height, output_format, text.encode()))
+        svg_errors = getattr(self, "_svg_errors", {})
+        svg_errors.clear()
+        rc = self.lib.smr_renderer_update_scene(self._h, output_id.encode(), width, height, output_format, text.encode())
+        if rc < 0 and svg_errors:  # an SVG rasteriser raised: its text goes with the library's
+            raise SceneError(self.lib.smr_renderer_last_error(self._h).decode() + ": " + "; ".join(svg_errors.values()))
+        self._check(rc)
         return self.nodes(output_id)
 
     def unregister_output(self, output_id: str):

@@ -192,6 +192,8 @@ pub struct smr_text_params {
 pub struct smr_text_run { pub glyphs: *const smr_glyph, pub n_glyphs: u32, pub atlas: *const u8, pub atlas_w: u32, pub atlas_h: u32 }
 pub type smr_text_measure_fn =
     Option<unsafe extern "C" fn(user: *mut c_void, params: *const smr_text_params, widest_line: *mut f32, line_count: *mut u32) -> c_int>;
+pub type smr_svg_rasterise_fn =
+    Option<unsafe extern "C" fn(user: *mut c_void, image_id: *const c_char, width: u32, height: u32, rgba: *mut u8, pitch_bytes: usize) -> c_int>;
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct smr_scene_node {
     pub kind: u32, pub parent: i32, pub n_children: u32, pub width: u32, pub height: u32,
