@@ -24,6 +24,13 @@ __device__ __forceinline__ int lanczos_taps(float scale) {
     return taps > MAX_TAPS ? MAX_TAPS : taps;
 }
 
+// sin / cos of an f32 argument rounded correctly: evaluated in f64 and rounded once.  That is what the host's sinf / cosf give the oracle;
+// the device library's f32 routines may be an ulp off, and the rotation below carries that ulp into every weight — enough to move a sum
+// across a rounding boundary of the f16 ring (tests/test_gpu_resample_zoo.py: a checkerboard's one value, copied down four columns).
+// Eight calls per output coordinate, in the weight builders only.
+__device__ __forceinline__ float lanczos_sin(float x) { return (float)sin((double)x); }
+__device__ __forceinline__ float lanczos_cos(float x) { return (float)cos((double)x); }
+
 // Weights of output coordinate `out_coord`: w[0..taps), returns first source index; *wsum = sum of weights.
 __device__ __forceinline__ int lanczos_weights(int out_coord, float scale, float offset, int taps, float *w, float *wsum) {
     const float PI = 3.14159265359f;
@@ -33,10 +40,10 @@ __device__ __forceinline__ int lanczos_weights(int out_coord, float scale, float
     float center = offset + ((float)out_coord + 0.5f) * scale - 0.5f;
     float first = ceilf(center - support);
     float x0 = (first - center) * inv_k;
-    float s1 = sinf(PI * x0), c1 = cosf(PI * x0);
-    float s3 = sinf(PI * x0 / 3.0f), c3 = cosf(PI * x0 / 3.0f);
-    float sd1 = sinf(PI * inv_k), cd1 = cosf(PI * inv_k);
-    float sd3 = sinf(PI * inv_k / 3.0f), cd3 = cosf(PI * inv_k / 3.0f);
+    float s1 = lanczos_sin(PI * x0), c1 = lanczos_cos(PI * x0);
+    float s3 = lanczos_sin(PI * x0 / 3.0f), c3 = lanczos_cos(PI * x0 / 3.0f);
+    float sd1 = lanczos_sin(PI * inv_k), cd1 = lanczos_cos(PI * inv_k);
+    float sd3 = lanczos_sin(PI * inv_k / 3.0f), cd3 = lanczos_cos(PI * inv_k / 3.0f);
     float sum = 0.0f;
     for (int t = 0; t < taps; t++) {
         float xx = x0 + (float)t * inv_k;

@@ -338,6 +338,23 @@ def test_large_box_reductions_keep_the_reference_sum_order(ctx, hip, dw, dh):
     assert np.abs(d.download().astype(np.int32) - want.astype(np.int32)).max() <= 1
 
 
+@pytest.mark.parametrize("sw,sh,fx,fy", [(2048, 2, 1024, 1), (4100, 3, 2048, 2), (1030, 5, 1024, 4), (3, 600, 1, 512), (40, 70, 32, 8)])
+def test_box_mean_over_several_groups_per_row_and_asymmetric_factors(ctx, hip, sw, sh, fx, fy):
+    """k_downsample_wave where the 1080p cases above never take it: factors of 1024 and 2048 across (two and four 512-texel groups per
+    source row — what a 4K child laid into a few pixels takes —, with a last reduced pixel that clamps at the edge), a column of 512 rows
+    one texel wide (one lane of each batch holds a texel), and 32 x 8, the smallest product the kernel is launched for.  White noise with
+    alpha, so that an addition out of the reference's order shows: f16 patterns equal to the oracle's bit for bit."""
+    assert fx * fy >= 256
+    src = np.random.default_rng(sw * 31 + fy).integers(0, 256, (sh, sw, 4), dtype=np.uint8)
+    red = ctx.surface((sw + fx - 1) // fx, (sh + fy - 1) // fy, hip.PX_RGBA16F)
+    red.upload(np.full((red.h, red.w, 4), 0x7E00, np.uint16))   # NaN patterns: a texel left unwritten cannot pass
+    ctx.downsample(ctx.surface_from(src), fx, fy, red)
+    want = orc.downsample(src, orc.PX_RGBA8_SRGB, fx, fy)
+    got = red.download()
+    assert got.shape == want.shape
+    assert (got.view(np.int16) == want.view(np.int16)).all(), int((got != want).sum())
+
+
 @pytest.mark.parametrize("srgb", [True, False])
 def test_rescale_bilinear(ctx, ctx_cpu, hip, srgb):
     c = ctx if srgb else ctx_cpu
