@@ -843,7 +843,8 @@ SMR_API int smr_renderer_add_lane(smr_renderer *r, smr_ctx *ctx);
  * GPU: SURVEY.md section 8e).  Per layout node and frame every remote input that exactly one texture layout resamples becomes its dst-sized
  * tile on the context that owns it (smr_ingest_resample_batch, one call per owner), the tiles are gathered on the renderer's own context
  * (smr_gather_tiles over a local communicator the renderer creates: one k_move_rects launch per owner) and composed there; an input that
- * does not fit that rule (1:1, sampled twice, a Shader node's child, the output's root, SMR_MODE_CPU_OPTIMIZED) has its raw planes moved
+ * does not fit that rule (1:1, sampled twice, a Shader node's child, the output's root, SMR_MODE_CPU_OPTIMIZED, a frame with an alpha channel,
+ * a one-axis or box-pre-reduced resample plan: those the owner would not run on the root's route) has its raw planes moved
  * to a root-resident frame by the same gather.  Every scene renders to the bytes the single-context renderer produces; smr_renderer_render
  * keeps its meaning (the frame of THIS pts, nothing blocks the host, smr_output_frame.ctx is the renderer's own context) and
  * smr_renderer_sync also waits for the shards.  Contexts on the root's own device get SMR_OPT_SHARED_DEVICE.

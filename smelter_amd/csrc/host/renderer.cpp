@@ -9,8 +9,9 @@
 // remote input that exactly one texture layout resamples is turned into its dst-sized tile ON ITS OWNER (smr_ingest_resample_batch, one call
 // per owner), the tiles travel to the root in one smr_gather_tiles (k_move_rects: one launch per owner) and the root's smr_render_layouts
 // samples the tile where a single context would have made it itself — the same bytes.  Whatever does not fit that rule (a 1:1 input, one
-// sampled twice, a Shader node's child, the output's root, SMR_MODE_CPU_OPTIMIZED) has its raw planes moved to a root-resident frame by the
-// same gather and is rendered exactly as on one context.
+// sampled twice, a Shader node's child, the output's root, SMR_MODE_CPU_OPTIMIZED, a resample plan the owner would run on another route than
+// the root: owner_takes_the_roots_route below) has its raw planes moved to a root-resident frame by the same gather and is rendered exactly
+// as on one context.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -526,6 +527,16 @@ int ensure_tile(smr_renderer *r, smr_ctx *ctx, smr_surface *&slot, uint32_t w, u
     if (slot && smr_surface_info_get(slot, &info) == 0 && info.width == w && info.height == h) return 0;
     return shard_gpu(r, ctx, smr_surface_create(ctx, w, h, SMR_PX_RGBA8, &slot), "shard tile");
 }
+// "The same bytes" holds for a tile only where the owner's smr_ingest_resample_batch runs the plan on the route the root's smr_render_layouts
+// would (smr_fused.hip: each walks a cascade of its own).  The cascades agree for a two-pass plan without box pre-reduction of a Y'CbCr
+// frame: fused conversion, plane source, RGB12 node, RGBA8 node (a vertical-first plan: the transposed node), the f32 kernel, the general
+// passes, in that order in both.  smr_render_layouts has matrix-core routes the batch entry point has not — the one-axis plans (kind 1), the
+// box-pre-reduced ones (levels != 0), the alpha builds for frames with an alpha channel: there the owner's tile is the general passes' (the
+// oracle's bytes) where the root's is the matrix-core kernel's (within 1 LSB of them), and a byte of the output could differ by one code from
+// the single-context renderer's.  Such an input travels as its raw planes.
+bool owner_takes_the_roots_route(const smr_frame *f, const smr_resample_plan &p) {
+    return frame_opaque(f) && p.kind == 2 && p.levels[0] == 0 && p.levels[1] == 0;
+}
 // A layout node's remote children, between its layout list (r->layouts) and its smr_render_layouts: tiles where the rule allows, staged
 // frames otherwise, ONE gather.  Rewrites r->layouts (crop = the whole tile) and srcs; kids keep describing the inputs themselves.
 int shard_layout_sources(smr_renderer *r, Output &o, std::vector<Source> &kids, std::vector<smr_source> &srcs) {
@@ -549,7 +560,7 @@ int shard_layout_sources(smr_renderer *r, Output &o, std::vector<Source> &kids, 
             const uint32_t dw = rw >= 1.0f ? (uint32_t)rw : 1u, dh = rh >= 1.0f ? (uint32_t)rh : 1u;
             smr_resample_plan plan;
             const int kind = smr_resample_plan_make(s.w, s.h, L->crop, dw, dh, &plan);
-            if (kind > 0 && dw <= 16384 && dh <= 16384) {
+            if (kind > 0 && dw <= 16384 && dh <= 16384 && owner_takes_the_roots_route(s.frame, plan)) {
                 ShardSlot &slot = o.l->shard[o.l->flip][s.node];
                 smr_ctx *oc = r->shard_ctx[s.owner];
                 smr_surface_info info;
@@ -572,7 +583,7 @@ int shard_layout_sources(smr_renderer *r, Output &o, std::vector<Source> &kids, 
                 b.crops.insert(b.crops.end(), L->crop, L->crop + 4);
                 b.dst.push_back(slot.tile_src);
                 g.owner.push_back(s.owner); g.src.push_back(slot.tile_src); g.dst.push_back(slot.tile_dst);
-                srcs[k].kind = frame_opaque(s.frame) ? (uint32_t)SMR_SOURCE_OPAQUE_SURFACE : (uint32_t)SMR_SOURCE_SURFACE;
+                srcs[k].kind = SMR_SOURCE_OPAQUE_SURFACE;  // (a Y'CbCr frame: owner_takes_the_roots_route)
                 srcs[k].surface = slot.tile_dst; srcs[k].frame = nullptr;
                 L->crop[0] = 0.0f; L->crop[1] = 0.0f; L->crop[2] = (float)dw; L->crop[3] = (float)dh;
                 tiled = true;

@@ -203,7 +203,9 @@ def test_what_cannot_travel_as_a_tile_falls_back_to_the_same_bytes(hip, name):
         pair.close()
 
 
-def test_a_non_opaque_remote_input_travels_as_a_plain_surface(hip):
+def test_a_non_opaque_remote_input_travels_as_its_raw_frame(hip):
+    """(A frame with an alpha channel is never tiled on its owner: the root's smr_render_layouts has the matrix-core kernel's alpha builds for it,
+    smr_ingest_resample_batch has not.)"""
     pair = Pair(hip, shards=1)
     try:
         _small_inputs(hip, pair, fmt=hip.FRAME_BGRA)
@@ -265,6 +267,48 @@ def test_two_outputs(hip):
         assert sorted(got) == ["a", "b"]
         pair.both(lambda r: r.unregister_output("a"))
         pair.render_equal(0.2, "one output left")
+    finally:
+        pair.close()
+
+
+def _box(i, w, h, **kw):
+    return {"type": "view", "background_color": "#203040FF", "children": [dict({"type": "rescaler", "top": 7.25, "left": 9.5, "width": w, "height": h, "child": _inp(i)}, **kw)]}
+
+
+# in1 (160 x 90) and in3 (36 x 64) live on the shard.  The plan of each scene's one remote input -> does it travel as a tile the owner resamples?
+ROUTE_SCENES = {
+    "one_axis_horizontal": (_box(1, 159.25, 89.6), False),    # 160 x 90 -> 159 x 90
+    "one_axis_vertical": (_box(3, 40, 63.25), False),         # 36 x 64 -> 36 x 63
+    "box_pre_reduced": (_box(1, 32, 18), False),              # a fifth: a box pre-reduction, then the residual
+    "vertical_first": (_box(1, 54, 40), True),                # 160 x 90 -> 54 x 30: the vertical scale is the larger one (both transpose)
+    "two_passes_horizontal_first": (_box(1, 80, 45), True),   # a half
+}
+
+
+@pytest.mark.parametrize("name", sorted(ROUTE_SCENES))
+def test_a_plan_the_owner_would_resample_on_another_route_travels_as_a_raw_frame(hip, name):
+    """smr_render_layouts on the root and smr_ingest_resample_batch on an owner choose a resampling route each.  They choose alike for a
+    two-pass plan without box pre-reduction of a Y'CbCr frame; for a one-axis plan and a pre-reduced one the root has matrix-core routes the
+    batch entry point has not (it runs the general passes: the oracle's bytes, where the matrix-core kernel is within 1 LSB of them), so a
+    tile made on the owner could differ from the single-context renderer's by one code.  Found by
+    tests/test_gpu_scene_walk.py (recorded in tests/golden/scene_walk_one_axis_on_a_shard.json: a 96 x 54 input at 95 x 54 mid-transition, one byte
+    of U); such an input travels as its raw
+    planes and the root resamples it as the single-context renderer does."""
+    from tests import scene_walk as SW
+    scene, tiled = ROUTE_SCENES[name]
+    pair = Pair(hip, shards=1)
+    try:
+        for i, (w, h) in enumerate([(160, 90), (160, 90), (128, 72), (36, 64)]):
+            pair.register_input(f"in{i}", hip.FRAME_PLANAR_YUVJ420, w, h, SW.frame_planes(["yuvj420", w, h, 1061427712 + i]))
+        assert pair.owner["in1"] is pair.shards[0] and pair.owner["in3"] is pair.shards[0]
+        assert pair.update("out", 384, 216, scene)
+        before = pair.shards[0].kernel_launches()
+        for k in range(2):
+            pair.render_equal(0.04 * k, f"{name} frame {k}")
+        ran = {key: v - before[key] for key, v in pair.shards[0].kernel_launches().items()}
+        resampled = sum(ran[key] for key in ("ingest_wave", "ingest_wave_rgba", "ingest_valu", "resample_general"))
+        assert ran["move_rects"] == 2, ran
+        assert (resampled >= 2) if tiled else (resampled == 0 and ran["frame_to_rgba"] == 0), (name, ran)
     finally:
         pair.close()
 
