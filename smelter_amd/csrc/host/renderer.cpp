@@ -56,11 +56,45 @@ namespace {
 // MAX_NODE_RESOLUTION (smelter-render/src/types.rs:146-149)
 constexpr uint32_t MAX_NODE_W = 7682, MAX_NODE_H = 4320;
 
+// Host memory that texels go to the device from — a painted page, a rasterised pixmap: tight rows of four bytes a texel.  Pinned where the GPU
+// half of the library is linked (smr_host_alloc: an upload is then a stream-ordered copy), plain memory without it.
+struct Staging {
+    void *host = nullptr;
+    size_t bytes = 0;
+    bool pinned = false;
+    static bool pinnable() { return smr_host_alloc && smr_host_free; }
+    // 0, or the status: smr_host_alloc's (c's last error says why), -2 when there is no plain memory
+    int alloc(smr_ctx *c, size_t n) {
+        if (pinnable()) {
+            const int rc = smr_host_alloc(c, n, &host);
+            if (rc < 0) return rc;
+            pinned = true;
+        } else {
+            host = malloc(n);
+            if (!host) return -2;
+        }
+        bytes = n;
+        return 0;
+    }
+    void release(smr_ctx *c) {
+        if (pinned) smr_host_free(c, host);
+        else free(host);
+        host = nullptr;
+    }
+    // Queues the copy into `f`, a frame of one packed plane of these texels, on c: stream-ordered from pinned memory, else smr_surface_upload
+    int upload(smr_ctx *c, const smr_frame &f) const {
+        if (pinned && smr_frame_upload_async) {
+            const void *const planes[3] = {host, nullptr, nullptr};
+            return smr_frame_upload_async(c, &f, planes);
+        }
+        return smr_surface_upload(c, f.planes[0], host, (size_t)f.width * 4);
+    }
+};
+
 // One registered web renderer instance (transformations/web_renderer/renderer.rs:27-35): the spec, the latest paint (frame_data) in pinned
 // staging, the latest rectangles (source_transforms) and, per lane, the page as that lane's context last uploaded it (website_texture).
 struct WebStaging {
-    void *host = nullptr;             // w * 4 * h bytes, tight rows
-    bool pinned = false;              // from smr_host_alloc (else plain memory: no GPU half)
+    Staging mem;                      // w * 4 * h bytes
     std::vector<smr_ctx *> in_flight; // contexts that queued an upload from it and were not seen idle since
 };
 struct WebLanePage {
@@ -297,10 +331,7 @@ void free_web_instance(smr_renderer *r, WebInstance &wi) {
     for (WebLanePage &lp : wi.lanes)
         if (lp.have) smr_frame_destroy(lp.ctx, &lp.page);
     wi.lanes.clear();
-    for (WebStaging &s : wi.staging) {
-        if (s.pinned) smr_host_free(r->lane_ctx[0], s.host);
-        else free(s.host);
-    }
+    for (WebStaging &s : wi.staging) s.mem.release(r->lane_ctx[0]);
     wi.staging.clear();
     wi.latest = -1;
 }
@@ -318,15 +349,8 @@ int web_staging_for_paint(smr_renderer *r, WebInstance &wi) {
         if (wi.staging[i].in_flight.empty()) return (int)i;
     if (wi.staging.size() < 4) {
         WebStaging s;
-        const size_t bytes = (size_t)wi.w * 4 * wi.h;
-        if (smr_host_alloc && smr_host_free) {
-            const int rc = gpu(r, smr_host_alloc(r->lane_ctx[0], bytes, &s.host), "web page staging");
-            if (rc < 0) return rc;
-            s.pinned = true;
-        } else {
-            s.host = malloc(bytes);
-            if (!s.host) return fail(r, -2, "web page staging: out of memory");
-        }
+        const int rc = s.mem.alloc(r->lane_ctx[0], (size_t)wi.w * 4 * wi.h);
+        if (rc < 0) return Staging::pinnable() ? gpu(r, rc, "web page staging") : fail(r, -2, "web page staging: out of memory");
         wi.staging.push_back(s);
         return (int)wi.staging.size() - 1;
     }
@@ -381,18 +405,10 @@ void release_unused_rasters(smr_renderer *r) {
 struct SvgPending {
     std::string id;
     uint32_t w = 0, h = 0;
-    void *host = nullptr;  // w * 4 * h bytes, tight rows, zero-filled before the call
-    bool pinned = false;   // from smr_host_alloc (else plain memory: no GPU half)
+    Staging mem;           // w * 4 * h bytes, zero-filled before the call
     smr_surface *surface = nullptr;
     bool opaque = false;
 };
-void free_svg_staging(smr_renderer *r, std::vector<SvgPending> &pend) {
-    for (SvgPending &p : pend) {
-        if (p.pinned) smr_host_free(r->lane_ctx[0], p.host);
-        else free(p.host);
-        p.host = nullptr;
-    }
-}
 // The rasters a new render graph needs and no resident one covers (SvgAsset::render_to_texture at the NODE's resolution, svg_image.rs:262-292):
 // the caller's rasteriser runs once per (asset, node width, node height), every new pixmap is uploaded into a surface of the node's size,
 // the colour fix-up runs in place — one smr_svg_nodes call, i.e. one launch per 16 rasters; none in CPU-optimized mode, where the pixmap's
@@ -415,19 +431,12 @@ int make_svg_rasters(smr_renderer *r, const std::vector<GraphNode> &nodes, std::
         if (w > MAX_NODE_W || h > MAX_NODE_H) { err = what + ": the node is above 7682 x 4320 (MAX_NODE_RESOLUTION)"; rc = -1; break; }
         SvgPending p;
         p.id = it->first; p.w = w; p.h = h;
-        const size_t bytes = (size_t)w * 4 * h;
-        if (smr_host_alloc && smr_host_free) {
-            rc = smr_host_alloc(r->lane_ctx[0], bytes, &p.host);
-            if (rc < 0) { err = what + ": pixmap staging: " + smr_last_error(r->lane_ctx[0]); break; }
-            p.pinned = true;
-        } else {
-            p.host = malloc(bytes);
-            if (!p.host) { err = what + ": pixmap staging: out of memory"; rc = -2; break; }
-        }
-        memset(p.host, 0, bytes);
+        rc = p.mem.alloc(r->lane_ctx[0], (size_t)w * 4 * h);
+        if (rc < 0) { err = what + ": pixmap staging: " + (Staging::pinnable() ? smr_last_error(r->lane_ctx[0]) : "out of memory"); break; }
+        memset(p.mem.host, 0, p.mem.bytes);
         pend.push_back(p);
         r->svg_calls++;
-        const int answer = img.svg_fn(img.svg_user, p.id.c_str(), w, h, (uint8_t *)p.host, (size_t)w * 4);
+        const int answer = img.svg_fn(img.svg_user, p.id.c_str(), w, h, (uint8_t *)p.mem.host, (size_t)w * 4);
         if (answer != 0) { err = what + ": the rasteriser failed (" + std::to_string(answer) + ")"; rc = -1; break; }
     }
     bool queued_work = false;
@@ -438,17 +447,12 @@ int make_svg_rasters(smr_renderer *r, const std::vector<GraphNode> &nodes, std::
         rc = smr_surface_create(r->lane_ctx[0], p.w, p.h, SMR_PX_RGBA8, &p.surface);
         if (rc < 0) { p.surface = nullptr; err = what + ": raster: " + smr_last_error(r->lane_ctx[0]); break; }
         fresh.push_back(p.surface);
-        if (p.pinned && smr_frame_upload_async) {
-            smr_frame f = {};
-            f.format = SMR_FRAME_RGBA; f.width = p.w; f.height = p.h; f.planes[0] = p.surface;
-            const void *const planes[3] = {p.host, nullptr, nullptr};
-            rc = smr_frame_upload_async(r->lane_ctx[0], &f, planes);
-        } else {
-            rc = smr_surface_upload(r->lane_ctx[0], p.surface, p.host, (size_t)p.w * 4);
-        }
+        smr_frame f = {};
+        f.format = SMR_FRAME_RGBA; f.width = p.w; f.height = p.h; f.planes[0] = p.surface;
+        rc = p.mem.upload(r->lane_ctx[0], f);
         queued_work = true;
         if (rc < 0) { err = what + ": upload: " + smr_last_error(r->lane_ctx[0]); break; }
-        const uint8_t *px = (const uint8_t *)p.host;
+        const uint8_t *px = (const uint8_t *)p.mem.host;
         p.opaque = true;
         for (size_t k = 0, n = (size_t)p.w * p.h; k < n && p.opaque; k++) p.opaque = px[4 * k + 3] == 255;
     }
@@ -461,7 +465,7 @@ int make_svg_rasters(smr_renderer *r, const std::vector<GraphNode> &nodes, std::
         const int e = smr_sync(r->lane_ctx[0]);
         if (e < 0 && rc >= 0) { rc = e; err = std::string("SVG rasters: ") + smr_last_error(r->lane_ctx[0]); }
     }
-    free_svg_staging(r, pend);
+    for (SvgPending &p : pend) p.mem.release(r->lane_ctx[0]);
     if (rc < 0) {
         for (smr_surface *s : fresh) smr_surface_destroy(r->lane_ctx[0], s);
         return rc;
@@ -746,9 +750,8 @@ int render_node(smr_renderer *r, Output &o, int idx, const FrameSetView &fs, Sou
         }
         if (lp.gen != wi.gen) {
             WebStaging &st = wi.staging[wi.latest];
-            if (smr_frame_upload_async) {
-                const void *planes[3] = {st.host, nullptr, nullptr};
-                rc = gpu(r, smr_frame_upload_async(r->ctx, &lp.page, planes), "web page upload");
+            if (smr_frame_upload_async) {  // (without the GPU half nothing is copied)
+                rc = gpu(r, st.mem.upload(r->ctx, lp.page), "web page upload");
                 if (rc < 0) return rc;
                 bool known = false;
                 for (smr_ctx *q : st.in_flight) known = known || q == r->ctx;
@@ -1163,7 +1166,7 @@ SMR_API int smr_renderer_web_paint(smr_renderer *r, const char *instance_id, con
     if (pitch_bytes < row) return fail(r, -1, "smr_renderer_web_paint: the pitch is below 4 * width");
     const int k = web_staging_for_paint(r, wi);
     if (k < 0) return k;
-    uint8_t *dst = (uint8_t *)wi.staging[k].host;
+    uint8_t *dst = (uint8_t *)wi.staging[k].mem.host;
     if (pitch_bytes == row) memcpy(dst, bgra, row * wi.h);
     else for (uint32_t y = 0; y < wi.h; y++) memcpy(dst + row * y, bgra + pitch_bytes * y, row);
     wi.latest = k;

@@ -814,17 +814,7 @@ __attribute__((visibility("default"))) int smr_svg_nodes(smr_ctx *ctx, smr_surfa
             if (surfaces[k] == surfaces[i]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_svg_nodes: entry %u repeats entry %u (the work is in place)", i, k);
     }
     StageScope scope(ctx, SMR_STAGE_INGEST);
-    for (uint32_t at = 0; at < n; at += SMR_SVG_MAX_JOBS) {
-        SvgBatch B;
-        memset(&B, 0, sizeof(B));
-        B.n = n - at < SMR_SVG_MAX_JOBS ? n - at : SMR_SVG_MAX_JOBS;
-        for (u32 i = 0; i < B.n; i++) B.j[i].px = view_of(surfaces[at + i]);
-        const u32 blocks = sv_plan(B);
-        if (!blocks) continue;
-        hipLaunchKernelGGL(k_svg_nodes, dim3(blocks), dim3(SMR_SVG_BLOCK), 0, ctx->stream, B, ctx->d_tables);
-        SMR_HIP(ctx, hipGetLastError());
-    }
-    return SMR_OK;
+    return nt_launch_batches<SvgBatch>(ctx, k_svg_nodes, n, [&](SvgJob &J, u32 k) { J.px = view_of(surfaces[k]); }, sv_plan);
 }
 
 }  // extern "C"

@@ -219,8 +219,8 @@ extern "C" __attribute__((visibility("default"))) int smr_web_view(smr_ctx *ctx,
             wv_layer_set(J.l[i], rects[at + i].x, rects[at + i].y, rects[at + i].width, rects[at + i].height, J.dst.w, J.dst.h);
         }
         if (!wv_plan(J)) continue;
-        dim3 grid(((u32)J.dst.w + SMR_WEB_TILE_W - 1) / SMR_WEB_TILE_W, ((u32)J.dst.h + SMR_WEB_TILE_H - 1) / SMR_WEB_TILE_H, 1);
-        hipLaunchKernelGGL(k_web_view, grid, dim3(SMR_WEB_BLOCK), 0, ctx->stream, J, ctx->d_tables);
+        dim3 grid(nt_tiles_x(J.dst.w), nt_tiles_y(J.dst.h), 1);
+        hipLaunchKernelGGL(k_web_view, grid, dim3(SMR_NODE_BLOCK), 0, ctx->stream, J, ctx->d_tables);
         SMR_HIP(ctx, hipGetLastError());
     }
     return SMR_OK;

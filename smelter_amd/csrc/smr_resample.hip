@@ -356,21 +356,11 @@ __attribute__((visibility("default"))) int smr_image_nodes(smr_ctx *ctx, const s
         if (src[i] == dst[i]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_image_nodes: pair %u draws a surface into itself", i);
     }
     StageScope scope(ctx, SMR_STAGE_RESAMPLE);
-    for (uint32_t at = 0; at < n; at += SMR_IMAGE_MAX_JOBS) {
-        ImageBatch B;
-        memset(&B, 0, sizeof(B));
-        B.n = n - at < SMR_IMAGE_MAX_JOBS ? n - at : SMR_IMAGE_MAX_JOBS;
-        for (u32 i = 0; i < B.n; i++) {
-            B.j[i].src = view_of(src[at + i]);
-            B.j[i].dst = view_of(dst[at + i]);
-            B.j[i].pxi = pxi_of(ctx, src[at + i]);
-        }
-        const u32 blocks = in_plan(B);
-        if (!blocks) continue;
-        hipLaunchKernelGGL(k_image_nodes, dim3(blocks), dim3(SMR_IMAGE_BLOCK), 0, ctx->stream, B, ctx->d_tables);
-        SMR_HIP(ctx, hipGetLastError());
-    }
-    return SMR_OK;
+    return nt_launch_batches<ImageBatch>(ctx, k_image_nodes, n, [&](ImageJob &J, u32 k) {
+        J.src = view_of(src[k]);
+        J.dst = view_of(dst[k]);
+        J.pxi = pxi_of(ctx, src[k]);
+    }, in_plan);
 }
 
 

@@ -70,6 +70,30 @@ __device__ __forceinline__ u32 srgb_encode8(float x, const float *__restrict__ t
 
 __device__ __forceinline__ float subtexel(float f) { return floorf(f * 256.0f + 0.5f) / 256.0f; }
 
+// The 8-bit halves of load_texel / store_texel: an RGBA8 word <-> its float4, per `pxi` (PXI_RGBA8_SRGB or PXI_RGBA8_UNORM), for kernels
+// that hold the word in a register.
+__device__ __forceinline__ float4 decode_rgba8(u32 raw, int pxi, const float *__restrict__ dec) {
+    const u32 r = raw & 0xff, g = (raw >> 8) & 0xff, b = (raw >> 16) & 0xff, a = raw >> 24;
+    float4 o;
+    if (pxi == PXI_RGBA8_SRGB) {
+        o.x = dec[r]; o.y = dec[g]; o.z = dec[b];
+    } else {
+        o.x = (float)r / 255.0f; o.y = (float)g / 255.0f; o.z = (float)b / 255.0f;
+    }
+    o.w = (float)a / 255.0f;
+    return o;
+}
+__device__ __forceinline__ u32 encode_rgba8(int pxi, const float4 &v, const float *__restrict__ thr) {
+    u32 r, g, b;
+    if (pxi == PXI_RGBA8_SRGB) {
+        r = srgb_encode8(v.x, thr); g = srgb_encode8(v.y, thr); b = srgb_encode8(v.z, thr);
+    } else {
+        r = unorm8(v.x); g = unorm8(v.y); b = unorm8(v.z);
+    }
+    u32 a = unorm8(v.w);
+    return r | (g << 8) | (b << 16) | (a << 24);
+}
+
 __device__ __forceinline__ float4 load_texel(const SurfView &s, int pxi, int x, int y, const float *__restrict__ dec) {
     float4 o;
     if (pxi == PXI_RGBA16F) {
@@ -78,14 +102,7 @@ __device__ __forceinline__ float4 load_texel(const SurfView &s, int pxi, int x, 
         float2 a = __half22float2(lo), b = __half22float2(hi);
         o = make_float4(a.x, a.y, b.x, b.y);
     } else {
-        const u32 raw = *(const u32 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 4);
-        u32 r = raw & 0xff, g = (raw >> 8) & 0xff, b = (raw >> 16) & 0xff, a = raw >> 24;
-        if (pxi == PXI_RGBA8_SRGB) {
-            o.x = dec[r]; o.y = dec[g]; o.z = dec[b];
-        } else {
-            o.x = (float)r / 255.0f; o.y = (float)g / 255.0f; o.z = (float)b / 255.0f;
-        }
-        o.w = (float)a / 255.0f;
+        return decode_rgba8(*(const u32 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 4), pxi, dec);
     }
     return o;
 }
@@ -99,14 +116,8 @@ __device__ __forceinline__ void store_texel(const SurfView &s, int pxi, int x, i
         raw.y = *(const u32 *)&hi;
         *(uint2 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 8) = raw;
     } else {
-        u32 r, g, b;
-        if (pxi == PXI_RGBA8_SRGB) {
-            r = srgb_encode8(v.x, thr); g = srgb_encode8(v.y, thr); b = srgb_encode8(v.z, thr);
-        } else {
-            r = unorm8(v.x); g = unorm8(v.y); b = unorm8(v.z);
-        }
-        u32 a = unorm8(v.w);
-        *(u32 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 4) = r | (g << 8) | (b << 16) | (a << 24);
+        const u32 word = encode_rgba8(pxi, v, thr);
+        *(u32 *)(s.ptr + (size_t)y * s.pitch + (size_t)x * 4) = word;
     }
 }
 

@@ -4,13 +4,9 @@
 // is done (transformations/image/svg_image.rs:120-167) — the premultiplied, gamma-encoded pixmap is un-premultiplied through the linear view,
 // quantised to 8 bits, and premultiplied through the sRGB view — where the two existing passes would be two launches per raster.
 //
-//   * The jobs travel BY VALUE in the kernel arguments (SvgBatch), as k_image_nodes' do: no table upload, nothing to keep alive.
-//   * A workgroup takes one tile of 64 x 16 texels of one job; SvgBatch::first_tile (a prefix sum over the jobs' tile counts, made by sv_plan
-//     on the host) maps blockIdx.x to (job, tile).  Every branch on a job's fields is uniform per workgroup.
-//   * Lane l of wave w owns the four consecutive texels x = 4 * (l & 15) .. + 3 of row 4 * w + (l >> 4) of the tile: it reads them, fixes
-//     them and writes them back where they were.  One 16-byte global load and one 16-byte global store where the group is whole and the
-//     surface's base and pitch are multiples of 16 (every surface smr_surface_create makes); a row's last, partial group and any other
-//     surface go texel by texel.
+//   * Jobs by value in the kernel arguments, one 64 x 16 tile of one job's surface per workgroup, four texels of a row per lane, 16-byte
+//     accesses where the surface allows: the geometry of smr_node_tiles.h.  A lane reads its group, fixes it and writes it back where it
+//     was, access by access (sv_workgroup says why not through the group helpers).
 //   * Per texel, exactly the two passes with the 8-bit word between them: k_premult mode 1's operations in its order
 //     (remove_premultiplied_alpha.wgsl:24-35), then k_premult mode 0 with PXI_RGBA8_SRGB on that word (add_premultiplied_alpha.wgsl:24-35).
 //     No special case for alpha 0 or 255: the function maps (c, alpha) to a byte, and the tests enumerate its 65 536 cases.
@@ -19,40 +15,29 @@
 // The source compiles under SMR_EMU (tests/emu/emu_svg_nodes.cpp): the CPU tests run it on guard-paged buffers.
 #pragma once
 
-#include "smr_internal.h"
+#include "smr_node_tiles.h"
 
-#define SMR_SVG_MAX_JOBS 16
-#define SMR_SVG_BLOCK 256
-#define SMR_SVG_TILE_W 64
-#define SMR_SVG_TILE_H 16
+// (this kernel's former names for the shared geometry: emulator drivers written against them still compile; the values are smr_node_tiles.h's)
+#define SMR_SVG_MAX_JOBS SMR_NODE_MAX_JOBS
+#define SMR_SVG_BLOCK SMR_NODE_BLOCK
+#define SMR_SVG_TILE_W SMR_NODE_TILE_W
+#define SMR_SVG_TILE_H SMR_NODE_TILE_H
 
 struct SvgJob {
     SurfView px;  // the pixmap as uploaded: premultiplied, gamma-encoded RGBA8; the node's bytes afterwards
-    u32 wide;     // 1: the surface's base and pitch are multiples of 16 — whole groups are one 16-byte load and one 16-byte store (sv_plan)
+    u32 wide;     // nt_wide(px) (sv_plan)
 };
 
 struct SvgBatch {
-    SvgJob j[SMR_SVG_MAX_JOBS];
-    u32 first_tile[SMR_SVG_MAX_JOBS + 1];  // first_tile[i] .. first_tile[i + 1]: the workgroups of job i
+    SvgJob j[SMR_NODE_MAX_JOBS];
+    u32 first_tile[SMR_NODE_MAX_JOBS + 1];  // first_tile[i] .. first_tile[i + 1]: the workgroups of job i
     u32 n;
 };
 
 // Fills everything of B but j[].px and n; returns the number of workgroups (0: nothing to fix).  Host code, shared with the emulator.
 // A job without a texel has no tile.
 static inline u32 sv_plan(SvgBatch &B) {
-    u32 total = 0;
-    for (u32 i = 0; i < SMR_SVG_MAX_JOBS; i++) {
-        B.first_tile[i] = total;
-        if (i >= B.n) continue;
-        SvgJob &J = B.j[i];
-        J.wide = 0;
-        if (!J.px.ptr || J.px.w <= 0 || J.px.h <= 0) continue;
-        J.wide = (((uintptr_t)J.px.ptr | J.px.pitch) & 15u) == 0 ? 1u : 0u;
-        const u32 tx = ((u32)J.px.w + SMR_SVG_TILE_W - 1) / SMR_SVG_TILE_W, ty = ((u32)J.px.h + SMR_SVG_TILE_H - 1) / SMR_SVG_TILE_H;
-        total += tx * ty;
-    }
-    B.first_tile[SMR_SVG_MAX_JOBS] = total;
-    return total;
+    return nt_plan(B, [](const SvgJob &J) { return &J.px; });
 }
 
 #ifdef __HIPCC__
@@ -77,22 +62,20 @@ __device__ __forceinline__ u32 sv_fix_texel(u32 p, const float *__restrict__ dec
 
 // What thread `tid` of workgroup `block` does.  Every branch on B's fields is uniform per workgroup.
 __device__ __forceinline__ void sv_workgroup(const SvgBatch &B, u32 block, u32 tid, const float *__restrict__ tables) {
-    if (block >= B.first_tile[SMR_SVG_MAX_JOBS]) return;
-    u32 i = 0;
-#pragma unroll 1
-    while (i + 1 < SMR_SVG_MAX_JOBS && block >= B.first_tile[i + 1]) i++;
+    if (block >= B.first_tile[SMR_NODE_MAX_JOBS]) return;
+    const u32 i = nt_job_of(B.first_tile, block);
     const SurfView px = B.j[i].px;
     const u32 wide = B.j[i].wide;
-    const u32 tiles_x = ((u32)px.w + SMR_SVG_TILE_W - 1) / SMR_SVG_TILE_W;
-    const u32 t = block - B.first_tile[i];
-    const u32 tile_y = t / tiles_x, tile_x = t - tile_y * tiles_x;
-    const int x0 = (int)(tile_x * SMR_SVG_TILE_W + 4u * (tid & 15u));
-    const int y = (int)(tile_y * SMR_SVG_TILE_H + 4u * (tid >> 6) + ((tid >> 4) & 3u));
+    const NodeTile T = nt_tile_of(B.first_tile, i, block, px.w);
+    const int x0 = (int)nt_lane_x(T.x * SMR_NODE_TILE_W, tid);
+    const int y = (int)nt_lane_y(T.y * SMR_NODE_TILE_H, tid);
     if (x0 >= px.w || y >= px.h) return;
     const float *dec = tables, *thr = tables + 256;
-    const int n = px.w - x0 < 4 ? px.w - x0 : 4;
+    const int n = px.w - x0;  // the texels the row has from x0 on: the group is min(n, 4) of them
     u8 *p = px.ptr + (size_t)y * px.pitch + (size_t)x0 * 4;
-    if (wide && n == 4) {
+    // (nt_load_group / nt_store_group with the texels fixed in between is other machine code — half the registers —, and this kernel's is
+    // held to what it was: the group is read, fixed and written back access by access here)
+    if (wide && n >= 4) {
         const uint4 v = g_ld_u32x4(p);
         g_st_u32x4(p, make_uint4(sv_fix_texel(v.x, dec, thr), sv_fix_texel(v.y, dec, thr), sv_fix_texel(v.z, dec, thr), sv_fix_texel(v.w, dec, thr)));
     } else {
@@ -103,7 +86,7 @@ __device__ __forceinline__ void sv_workgroup(const SvgBatch &B, u32 block, u32 t
 }
 
 #ifndef SMR_EMU
-__global__ void __launch_bounds__(SMR_SVG_BLOCK) k_svg_nodes(const SvgBatch B, const float *__restrict__ tables) {
+__global__ void __launch_bounds__(SMR_NODE_BLOCK) k_svg_nodes(const SvgBatch B, const float *__restrict__ tables) {
     sv_workgroup(B, blockIdx.x, threadIdx.x, tables);
 }
 #endif

@@ -5,8 +5,8 @@
 // enqueue is half of the frame period (profiles/r06_host_rate.txt): the argument that produced k_move_rects and k_image_nodes.
 //
 //   * The job travels BY VALUE in the kernel arguments (WebJob): no table upload, no host synchronisation, nothing to keep alive.
-//   * A workgroup of 256 takes one tile of 64 x 16 destination texels; lane l of wave w owns the four consecutive texels
-//     x = 4 * (l & 15) .. + 3 of row 4 * w + (l >> 4) of the tile, the running colour of each held in a register as its RGBA8 word.
+//   * One 64 x 16 tile of the destination per workgroup of a 2-D grid, four texels of a row per lane (smr_node_tiles.h: the lane mapping
+//     and the group load / store; not its job table — there is one job), the running colour of each held in a register as its RGBA8 word.
 //   * Page texel: one dword load, B and R exchanged by a byte permute (render_website.wgsl:36-40).  As the first layer (the page below the
 //     children) it IS the running colour: encode(decode(b)) == b, so a blend onto the transparent target leaves the very bytes.  As the last
 //     layer (the page above the children) it is decoded and blended like any other.
@@ -18,10 +18,8 @@
 //   * A layer whose bounds miss the workgroup's tile is skipped by a workgroup-uniform branch; a tile no child touches is a pure swizzled
 //     copy of 16-byte groups.
 //   * A node with more than 16 children continues with further launches that LOAD the destination instead of clearing it (WebJob::load).
-//   * The four results leave as one 16-byte global store when the group is whole and the destination's base and pitch are multiples of 16
-//     (every surface smr_surface_create makes); a row's last, partial group and any other destination go texel by texel.  The page (and a
-//     loaded destination) is read the same way.
-//   * Nothing outside [0, w) x [0, h) of the destination is written: not its row padding, not a byte behind its last row.
+//   * The four results leave as a group (nt_store_group); the page (and a loaded destination) is read as one (nt_load_group).  Nothing
+//     outside [0, w) x [0, h) of the destination is written.
 //   * No LDS, no barrier: threads do not talk to each other.  Vector stores only.
 // hipcc --offload-arch=gfx950 -O3 --save-temps reports for k_web_view: 57 VGPRs, 0 AGPRs, 50 SGPRs, no scratch, no LDS, 8 waves per SIMD.
 // The source compiles under SMR_EMU (tests/emu/emu_web_view.cpp): the CPU tests run it on guard-paged buffers.
@@ -30,11 +28,14 @@
 #include <cmath>
 
 #include "smr_layout_dev.h"
+#include "smr_node_tiles.h"
+
+// (this kernel's former names for the shared geometry: emulator drivers written against them still compile; the values are smr_node_tiles.h's)
+#define SMR_WEB_BLOCK SMR_NODE_BLOCK
+#define SMR_WEB_TILE_W SMR_NODE_TILE_W
+#define SMR_WEB_TILE_H SMR_NODE_TILE_H
 
 #define SMR_WEB_MAX_LAYERS 16
-#define SMR_WEB_BLOCK 256
-#define SMR_WEB_TILE_W 64
-#define SMR_WEB_TILE_H 16
 
 enum { WV_PAGE_NONE = 0, WV_PAGE_BELOW = 1, WV_PAGE_ABOVE = 2 };
 
@@ -51,8 +52,8 @@ struct WebJob {
     int pxi;             // PXI_RGBA8_SRGB / PXI_RGBA8_UNORM: how texels are decoded and encoded
     u32 page_mode;       // WV_PAGE_NONE: children only | _BELOW: the page is the first layer, on the cleared target | _ABOVE: the last layer
     u32 load;            // 1: the running colour starts from the destination's texels (a continuation launch), 0: from transparent
-    u32 wide;            // 1: the destination's base and pitch are multiples of 16 — whole groups leave as one 16-byte store
-    u32 page_wide;       // ... and the page's: whole groups arrive as one 16-byte load
+    u32 wide;            // nt_wide(dst): whole groups leave as one 16-byte store
+    u32 page_wide;       // nt_wide(page): whole groups arrive as one 16-byte load
 };
 
 // Layer `L`'s rectangle and the pixels it covers on a page of page_w x page_h.  Host code, shared with the emulator.  Pixel px is covered
@@ -83,8 +84,8 @@ static inline void wv_launch_set(WebJob &J, u32 k, u32 n, int under) {
 
 // Fills wide / page_wide; returns false when the job has no texel to write.
 static inline bool wv_plan(WebJob &J) {
-    J.wide = (((uintptr_t)J.dst.ptr | J.dst.pitch) & 15u) == 0 ? 1u : 0u;
-    J.page_wide = (((uintptr_t)J.page.ptr | J.page.pitch) & 15u) == 0 ? 1u : 0u;
+    J.wide = nt_wide(J.dst);
+    J.page_wide = nt_wide(J.page);
     return J.dst.ptr && J.dst.w > 0 && J.dst.h > 0 && (J.page_mode == WV_PAGE_NONE || J.page.ptr);
 }
 
@@ -99,51 +100,26 @@ __device__ __forceinline__ u32 wv_swizzle(u32 v) {
 #endif
 }
 
-// load_texel's decode (smr_shader_dev.h) of an RGBA8 word that is in a register already
-__device__ __forceinline__ float4 wv_decode(u32 raw, int pxi, const float *__restrict__ dec) {
-    const u32 r = raw & 0xff, g = (raw >> 8) & 0xff, b = (raw >> 16) & 0xff, a = raw >> 24;
-    float4 o;
-    if (pxi == PXI_RGBA8_SRGB) {
-        o.x = dec[r]; o.y = dec[g]; o.z = dec[b];
-    } else {
-        o.x = (float)r / 255.0f; o.y = (float)g / 255.0f; o.z = (float)b / 255.0f;
-    }
-    o.w = (float)a / 255.0f;
-    return o;
-}
-
-// the n (1 .. 4) texels of a group at p: one 16-byte load where the surface allows and the group is whole
-__device__ __forceinline__ void wv_load_group(const u8 *p, u32 wide, int n, u32 out[4]) {
-    if (wide && n == 4) {
-        const uint4 v = g_ld_u32x4(p);
-        out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < n) out[k] = g_ld_u32(p + 4 * k);
-    }
-}
-
 // What thread `tid` of workgroup (bx, by) does.  Every branch on J's fields and on the tile is uniform per workgroup.
 __device__ __forceinline__ void wv_workgroup(const WebJob &J, u32 bx, u32 by, u32 tid, const float *__restrict__ tables) {
     const SurfView dst = J.dst;
-    const int tx0 = (int)(bx * SMR_WEB_TILE_W), ty0 = (int)(by * SMR_WEB_TILE_H);
-    const int x0 = tx0 + (int)(4u * (tid & 15u));
-    const int y = ty0 + (int)(4u * (tid >> 6) + ((tid >> 4) & 3u));
+    const int tx0 = (int)(bx * SMR_NODE_TILE_W), ty0 = (int)(by * SMR_NODE_TILE_H);
+    const int x0 = tx0 + (int)nt_lane_x(0u, tid);
+    const int y = ty0 + (int)nt_lane_y(0u, tid);
     if (x0 >= dst.w || y >= dst.h) return;
     const float *dec = tables, *thr = tables + 256;
     const int pxi = J.pxi;
     const int srgb = pxi == PXI_RGBA8_SRGB ? 1 : 0;
-    const int n = dst.w - x0 < 4 ? dst.w - x0 : 4;
+    const int n = dst.w - x0;  // the texels the row has from x0 on: the group is min(n, 4) of them
     u8 *p = dst.ptr + (size_t)y * dst.pitch + (size_t)x0 * 4;
     u32 acc[4] = {0u, 0u, 0u, 0u};  // RGBA8 of the cleared target (wgpu::Color::TRANSPARENT, shader.rs:65)
     u32 pg[4] = {0u, 0u, 0u, 0u};
     if (J.page_mode != WV_PAGE_NONE) {
-        wv_load_group(J.page.ptr + (size_t)y * J.page.pitch + (size_t)x0 * 4, J.page_wide, n, pg);
+        nt_load_group(J.page.ptr + (size_t)y * J.page.pitch + (size_t)x0 * 4, J.page_wide, n, pg);
 #pragma unroll
         for (int k = 0; k < 4; k++) pg[k] = wv_swizzle(pg[k]);
     }
-    if (J.load) wv_load_group(p, J.wide, n, acc);
+    if (J.load) nt_load_group(p, J.wide, n, acc);
     if (J.page_mode == WV_PAGE_BELOW) {
 #pragma unroll
         for (int k = 0; k < 4; k++) acc[k] = pg[k];
@@ -152,7 +128,7 @@ __device__ __forceinline__ void wv_workgroup(const WebJob &J, u32 bx, u32 by, u3
 #pragma unroll 1
     for (u32 i = 0; i < J.n; i++) {
         const int lx0 = J.l[i].x0, ly0 = J.l[i].y0, lx1 = J.l[i].x1, ly1 = J.l[i].y1;
-        if (lx1 <= tx0 || lx0 >= tx0 + SMR_WEB_TILE_W || ly1 <= ty0 || ly0 >= ty0 + SMR_WEB_TILE_H || lx0 >= lx1 || ly0 >= ly1) continue;  // (uniform)
+        if (lx1 <= tx0 || lx0 >= tx0 + SMR_NODE_TILE_W || ly1 <= ty0 || ly0 >= ty0 + SMR_NODE_TILE_H || lx0 >= lx1 || ly0 >= ly1) continue;  // (uniform)
         if (y < ly0 || y >= ly1) continue;
         const SurfView src = J.l[i].src;
         const float lx = J.l[i].x, lw = J.l[i].w;
@@ -169,19 +145,13 @@ __device__ __forceinline__ void wv_workgroup(const WebJob &J, u32 bx, u32 by, u3
     if (J.page_mode == WV_PAGE_ABOVE) {
 #pragma unroll
         for (int k = 0; k < 4; k++)
-            if (k < n) acc[k] = blend_store(acc[k], wv_decode(pg[k], pxi, dec), srgb, dec, thr);
+            if (k < n) acc[k] = blend_store(acc[k], decode_rgba8(pg[k], pxi, dec), srgb, dec, thr);
     }
-    if (J.wide && n == 4) {
-        g_st_u32x4(p, make_uint4(acc[0], acc[1], acc[2], acc[3]));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (k < n) g_st_u32(p + 4 * k, acc[k]);
-    }
+    nt_store_group(p, J.wide, n, acc);
 }
 
 #ifndef SMR_EMU
-__global__ void __launch_bounds__(SMR_WEB_BLOCK) k_web_view(const WebJob J, const float *__restrict__ tables) {
+__global__ void __launch_bounds__(SMR_NODE_BLOCK) k_web_view(const WebJob J, const float *__restrict__ tables) {
     wv_workgroup(J, blockIdx.x, blockIdx.y, threadIdx.x, tables);
 }
 #endif

@@ -2,24 +2,10 @@
 //
 // k_image_nodes' source (smelter_amd/csrc/smr_image_nodes.h: in_plan on the host, in_workgroup per thread) compiled for the CPU, so that
 // tests/test_emu_image_nodes.py can run one launch — every workgroup, every thread, in turn: threads do not talk to each other — on buffers
-// that are exactly as large as the surfaces they hold (emu_guard.h: the byte after, or before, them is an unmapped page).  Same shims as
-// emu_move.cpp.  The reference it is held against is made here too: a loop over sample_rgba_bilinear and store_texel (smr_shader_dev.h),
+// that are exactly as large as the surfaces they hold (emu_guard.h: the byte after, or before, them is an unmapped page).  Shims, tables and
+// the alignment rule: emu_node_kernel.h.  The reference it is held against is made here too: a loop over sample_rgba_bilinear and store_texel (smr_shader_dev.h),
 // one texel at a time — what k_rescale_bilinear does.
-#include <vector>
-
-#include <hip/hip_runtime.h>
-
-thread_local dim3 threadIdx, blockIdx;
-dim3 gridDim, blockDim;
-
-#include "emu_device.h"
-#include "emu_guard.h"
-EmuBlock *emu_blk = nullptr;
-thread_local unsigned char *emu_smem = nullptr;
-void __syncthreads() {}
-
-#include "smr_internal.h"
-#include "smr_tables.h"
+#include "emu_node_kernel.h"
 #include "smr_image_nodes.h"
 
 // Job i: the tight src_w[i] x src_h[i] RGBA8 texels src_px[i] drawn into dst_w[i] x dst_h[i].  The source sits in a buffer of exactly
@@ -29,21 +15,12 @@ void __syncthreads() {}
 // Returns the number of workgroups the launch has, or < 0.
 extern "C" int emu_image_nodes(int n, const u8 *const *src_px, const int *src_w, const int *src_h, const int *dst_w, const int *dst_h,
                                const u32 *dst_pitch, const u32 *dst_off, int srgb, u8 *const *dst_out, u8 *const *ref_out, u32 *wide_out) {
-    if (n < 0 || n > SMR_IMAGE_MAX_JOBS) return -1;
-    static float tables_src[SMR_TABLE_FLOATS];
-    static u32 lut16[SMR_LUT16_WORDS];
-    static bool have_tables = false;
-    if (!have_tables) {
-        if (!smr_build_tables(tables_src, lut16)) return -9;
-        have_tables = true;
-    }
-    GuardBuf tables;
-    tables.alloc(sizeof(tables_src), 0, 16);
-    memcpy(tables.ptr, tables_src, sizeof(tables_src));
-    const float *tab = (const float *)tables.ptr;
+    if (n < 0 || n > SMR_NODE_MAX_JOBS) return -1;
+    const EmuTables tables;
+    if (!tables.ptr) return -9;
+    const float *tab = tables.ptr;
     const int pxi = srgb ? PXI_RGBA8_SRGB : PXI_RGBA8_UNORM;
-    // (guard mode 1 puts a buffer's END on the guard page: its start then has the alignment of its size, 4 at least)
-    const size_t align = emu_guard_mode == 1 ? 4 : 16;
+    const size_t align = emu_surface_align();
 
     std::vector<GuardBuf> src((size_t)n), dst((size_t)n);
     std::vector<size_t> dst_bytes((size_t)n);
@@ -67,7 +44,7 @@ extern "C" int emu_image_nodes(int n, const u8 *const *src_px, const int *src_w,
     for (int i = 0; i < n; i++) wide_out[i] = B.j[i].wide;
     // (one workgroup more than the launch has: it must do nothing)
     for (u32 blk = 0; blk <= blocks; blk++)
-        for (u32 tid = 0; tid < SMR_IMAGE_BLOCK; tid++) in_workgroup(B, blk, tid, tab);
+        for (u32 tid = 0; tid < SMR_NODE_BLOCK; tid++) in_workgroup(B, blk, tid, tab);
     for (int i = 0; i < n; i++) {
         if (dst_bytes[i]) memcpy(dst_out[i], dst[i].ptr, dst_bytes[i]);
         if (dst_w[i] == 0 || dst_h[i] == 0) continue;

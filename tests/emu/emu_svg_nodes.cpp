@@ -2,25 +2,11 @@
 //
 // k_svg_nodes' source (smelter_amd/csrc/smr_svg_nodes.h: sv_plan on the host, sv_workgroup per thread) compiled for the CPU, so that
 // tests/test_emu_svg_nodes.py can run one launch — every workgroup, every thread, in turn: threads do not talk to each other — on buffers
-// that are exactly as large as the surfaces they hold (emu_guard.h: the byte after, or before, them is an unmapped page).  Same shims as
-// emu_image_nodes.cpp.  The work is in place, so the store mask is held here: every byte of a buffer outside the job's texels — the bytes
+// that are exactly as large as the surfaces they hold (emu_guard.h: the byte after, or before, them is an unmapped page).  Shims, tables and the
+// alignment rule: emu_node_kernel.h.  The work is in place, so the store mask is held here: every byte of a buffer outside the job's texels — the bytes
 // before its base, its row padding — is compared with what it held before the launch (a seeded pattern in guard mode 3, as emu_pad_fill
 // makes it; a sentinel otherwise).
-#include <vector>
-
-#include <hip/hip_runtime.h>
-
-thread_local dim3 threadIdx, blockIdx;
-dim3 gridDim, blockDim;
-
-#include "emu_device.h"
-#include "emu_guard.h"
-EmuBlock *emu_blk = nullptr;
-thread_local unsigned char *emu_smem = nullptr;
-void __syncthreads() {}
-
-#include "smr_internal.h"
-#include "smr_tables.h"
+#include "emu_node_kernel.h"
 #include "smr_svg_nodes.h"
 
 static inline u8 outside_byte(size_t off, u32 seed) { return emu_guard_mode == 3 ? emu_pad_byte(off, seed) : (u8)0xc3; }
@@ -30,20 +16,11 @@ static inline u8 outside_byte(size_t off, u32 seed) { return emu_guard_mode == 3
 // wide_out[i]: 1 = whole groups went as 16-byte accesses.  Returns the number of workgroups the launch has, -77 after naming a byte outside
 // a job's texels that changed, or another value < 0.
 extern "C" int emu_svg_nodes(int n, const u8 *const *px_in, const int *w, const int *h, const u32 *pitch, const u32 *off, u8 *const *px_out, u32 *wide_out) {
-    if (n < 0 || n > SMR_SVG_MAX_JOBS) return -1;
-    static float tables_src[SMR_TABLE_FLOATS];
-    static u32 lut16[SMR_LUT16_WORDS];
-    static bool have_tables = false;
-    if (!have_tables) {
-        if (!smr_build_tables(tables_src, lut16)) return -9;
-        have_tables = true;
-    }
-    GuardBuf tables;
-    tables.alloc(sizeof(tables_src), 0, 16);
-    memcpy(tables.ptr, tables_src, sizeof(tables_src));
-    const float *tab = (const float *)tables.ptr;
-    // (guard mode 1 puts a buffer's END on the guard page: its start then has the alignment of its size, 4 at least)
-    const size_t align = emu_guard_mode == 1 ? 4 : 16;
+    if (n < 0 || n > SMR_NODE_MAX_JOBS) return -1;
+    const EmuTables tables;
+    if (!tables.ptr) return -9;
+    const float *tab = tables.ptr;
+    const size_t align = emu_surface_align();
 
     std::vector<GuardBuf> buf((size_t)n);
     std::vector<size_t> bytes((size_t)n);
@@ -65,7 +42,7 @@ extern "C" int emu_svg_nodes(int n, const u8 *const *px_in, const int *w, const 
     for (int i = 0; i < n; i++) wide_out[i] = B.j[i].wide;
     // (one workgroup more than the launch has: it must do nothing)
     for (u32 blk = 0; blk <= blocks; blk++)
-        for (u32 tid = 0; tid < SMR_SVG_BLOCK; tid++) sv_workgroup(B, blk, tid, tab);
+        for (u32 tid = 0; tid < SMR_NODE_BLOCK; tid++) sv_workgroup(B, blk, tid, tab);
     for (int i = 0; i < n; i++) {
         const bool empty = w[i] == 0 || h[i] == 0;
         const size_t row = empty ? 0 : (size_t)w[i] * 4;

@@ -3,22 +3,8 @@
 // k_web_view's source (smelter_amd/csrc/smr_web_view.h: wv_layer_set / wv_launch_set / wv_plan on the host, wv_workgroup per thread) compiled
 // for the CPU, so that tests/test_emu_web_view.py can run a WebView node's launches — every workgroup, every thread, in turn: threads do not
 // talk to each other — on buffers that are exactly as large as the surfaces they hold (emu_guard.h: the byte after, or before, them is an
-// unmapped page).  Same shims as emu_image_nodes.cpp.  The launches are made the way smr_web_view (smr_layout.hip) makes them.
-#include <vector>
-
-#include <hip/hip_runtime.h>
-
-thread_local dim3 threadIdx, blockIdx;
-dim3 gridDim, blockDim;
-
-#include "emu_device.h"
-#include "emu_guard.h"
-EmuBlock *emu_blk = nullptr;
-thread_local unsigned char *emu_smem = nullptr;
-void __syncthreads() {}
-
-#include "smr_internal.h"
-#include "smr_tables.h"
+// unmapped page).  Shims, tables and the alignment rule: emu_node_kernel.h.  The launches are made the way smr_web_view (smr_layout.hip) makes them.
+#include "emu_node_kernel.h"
 #include "smr_web_view.h"
 
 // The page: w x h BGRA8 texels page_px (tight) in a buffer whose rows are page_pitch bytes apart (exactly page_pitch * (h - 1) + w * 4
@@ -29,19 +15,10 @@ void __syncthreads() {}
 extern "C" int emu_web_view(const u8 *page_px, int w, int h, u32 page_pitch, int n, const u8 *const *src_px, const int *src_w, const int *src_h,
                             const float *rects, int under, int srgb, u32 dst_pitch, u32 dst_off, u8 *dst_out, u32 *info_out) {
     if (w <= 0 || h <= 0 || n < 0 || page_pitch < (u32)w * 4 || dst_pitch < (u32)w * 4) return -1;
-    static float tables_src[SMR_TABLE_FLOATS];
-    static u32 lut16[SMR_LUT16_WORDS];
-    static bool have_tables = false;
-    if (!have_tables) {
-        if (!smr_build_tables(tables_src, lut16)) return -9;
-        have_tables = true;
-    }
-    GuardBuf tables;
-    tables.alloc(sizeof(tables_src), 0, 16);
-    memcpy(tables.ptr, tables_src, sizeof(tables_src));
-    const float *tab = (const float *)tables.ptr;
-    // (guard mode 1 puts a buffer's END on the guard page: its start then has the alignment of its size, 4 at least)
-    const size_t align = emu_guard_mode == 1 ? 4 : 16;
+    const EmuTables tables;
+    if (!tables.ptr) return -9;
+    const float *tab = tables.ptr;
+    const size_t align = emu_surface_align();
 
     GuardBuf page, dst;
     page.alloc((size_t)page_pitch * (h - 1) + (size_t)w * 4, 0x5a, align);
@@ -54,7 +31,7 @@ extern "C" int emu_web_view(const u8 *page_px, int w, int h, u32 page_pitch, int
         src[i].alloc((size_t)src_w[i] * 4 * src_h[i], 0, align);
         memcpy(src[i].ptr, src_px[i], (size_t)src_w[i] * 4 * src_h[i]);
     }
-    const u32 tiles_x = ((u32)w + SMR_WEB_TILE_W - 1) / SMR_WEB_TILE_W, tiles_y = ((u32)h + SMR_WEB_TILE_H - 1) / SMR_WEB_TILE_H;
+    const u32 tiles_x = nt_tiles_x(w), tiles_y = nt_tiles_y(h);
     info_out[0] = info_out[1] = info_out[2] = 0;
     for (u32 k = 0; k < wv_launches((u32)n); k++) {
         WebJob J;
@@ -73,7 +50,7 @@ extern "C" int emu_web_view(const u8 *page_px, int w, int h, u32 page_pitch, int
         // (one row and one column of workgroups more than the launch has: they must do nothing)
         for (u32 by = 0; by <= tiles_y; by++)
             for (u32 bx = 0; bx <= tiles_x; bx++)
-                for (u32 tid = 0; tid < SMR_WEB_BLOCK; tid++) wv_workgroup(J, bx, by, tid, tab);
+                for (u32 tid = 0; tid < SMR_NODE_BLOCK; tid++) wv_workgroup(J, bx, by, tid, tab);
     }
     memcpy(dst_out, dst.ptr, dst_bytes);
     return (int)(tiles_x * tiles_y);

@@ -13,17 +13,11 @@
 #include <string>
 #include <vector>
 
-#include "smr.h"
+#define SAN_DRIVER "animated_driver"
+#include "san_driver.h"
 
 extern "C" long null_device_live_surfaces();
 extern "C" void null_device_fail_after(long n);
-
-static long g_checks = 0;
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        g_checks++;                                                                              \
-        if (!(cond)) { fprintf(stderr, "animated_driver:%d: %s does not hold\n", __LINE__, #cond); exit(1); } \
-    } while (0)
 
 static const uint32_t W = 12, H = 10, N = 4;
 static const uint64_t MS = 1000000ull;

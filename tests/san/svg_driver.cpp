@@ -16,55 +16,22 @@
 #include <string>
 #include <vector>
 
-#include "smr.h"
+#define SAN_DRIVER "svg_driver"
+#include "san_driver.h"
 
 extern "C" long null_device_live_surfaces();
 extern "C" void null_device_fail_after(long n);
 
-static long g_checks = 0;
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        g_checks++;                                                                              \
-        if (!(cond)) { fprintf(stderr, "svg_driver:%d: %s does not hold\n", __LINE__, #cond); exit(1); } \
-    } while (0)
-
-// ---- the stand-ins
-static long g_live_staging = 0, g_uploads = 0, g_fix_calls = 0, g_fixed = 0;
-static long g_staging_fail = -1;  // the n-th smr_host_alloc from now fails
-static volatile uint64_t g_sink;
-
-static void touch(const void *p, size_t n) {
-    const uint8_t *b = (const uint8_t *)p;
-    uint64_t s = 0;
-    for (size_t i = 0; i < n; i++) s += b[i];
-    g_sink = s;
-}
+// ---- the stand-ins (staging and upload: san_driver.h)
+static long g_fix_calls = 0, g_fixed = 0;
 
 extern "C" {
-int smr_host_alloc(smr_ctx *ctx, size_t bytes, void **out) {
-    if (!ctx || !out || !bytes) return SMR_ERR_INVALID;
-    *out = nullptr;
-    if (g_staging_fail >= 0 && g_staging_fail-- == 0) return SMR_ERR_OOM;
-    *out = malloc(bytes);
-    if (!*out) return SMR_ERR_OOM;
-    memset(*out, 0xee, bytes);
-    g_live_staging++;
-    return SMR_OK;
-}
-void smr_host_free(smr_ctx *ctx, void *p) {
-    (void)ctx;
-    if (!p) return;
-    g_live_staging--;
-    free(p);
-}
+int smr_host_alloc(smr_ctx *ctx, size_t bytes, void **out) { return san_host_alloc(ctx, bytes, out); }
+void smr_host_free(smr_ctx *ctx, void *p) { san_host_free(ctx, p); }
 int smr_frame_upload_async(smr_ctx *ctx, const smr_frame *f, const void *const host_planes[3]) {
-    if (!ctx || !f || !host_planes || !host_planes[0]) return SMR_ERR_INVALID;
     smr_surface_info si;
-    if (f->format != SMR_FRAME_RGBA || smr_surface_info_get(f->planes[0], &si) != 0 || si.width != f->width || si.height != f->height || si.format != SMR_PX_RGBA8)
-        return SMR_ERR_INVALID;
-    touch(host_planes[0], (size_t)f->width * 4 * f->height);
-    g_uploads++;
-    return SMR_OK;
+    if (!f || smr_surface_info_get(f->planes[0], &si) != 0 || si.format != SMR_PX_RGBA8) return SMR_ERR_INVALID;
+    return san_frame_upload(ctx, f, host_planes, SMR_FRAME_RGBA);
 }
 int smr_svg_nodes(smr_ctx *ctx, smr_surface *const *surfaces, uint32_t n) {
     if (!ctx || (n && !surfaces)) return SMR_ERR_INVALID;

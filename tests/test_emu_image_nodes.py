@@ -33,7 +33,7 @@ SHAPES = [(160, 90, 1, 1), (160, 90, 65, 5), (3, 2, 67, 9), (5, 5, 5, 5), (7, 3,
 
 
 def load_emu():
-    h = C.CDLL(emu_build.build("smr_emu_image_nodes", "emu_image_nodes.cpp", ("smr_image_nodes.h", "smr_shader_dev.h", "smr_tables.h")))
+    h = C.CDLL(emu_build.build("smr_emu_image_nodes", "emu_image_nodes.cpp", ("smr_image_nodes.h", "smr_node_tiles.h", "../../tests/emu/emu_node_kernel.h", "smr_shader_dev.h", "smr_tables.h")))
     h.emu_image_nodes.argtypes = [C.c_int, C.POINTER(P8), PI, PI, PI, PI, PU, PU, C.c_int, C.POINTER(P8), C.POINTER(P8), PU]
     h.emu_image_nodes.restype = C.c_int
     return h

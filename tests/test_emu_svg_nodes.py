@@ -33,7 +33,7 @@ HEIGHTS = (1, 15, 16, 17)
 
 
 def load_emu():
-    h = C.CDLL(emu_build.build("smr_emu_svg_nodes", "emu_svg_nodes.cpp", ("smr_svg_nodes.h", "smr_shader_dev.h", "smr_tables.h")))
+    h = C.CDLL(emu_build.build("smr_emu_svg_nodes", "emu_svg_nodes.cpp", ("smr_svg_nodes.h", "smr_node_tiles.h", "../../tests/emu/emu_node_kernel.h", "smr_shader_dev.h", "smr_tables.h")))
     h.emu_svg_nodes.argtypes = [C.c_int, C.POINTER(P8), PI, PI, PU, PU, C.POINTER(P8), PU]
     h.emu_svg_nodes.restype = C.c_int
     return h

@@ -37,7 +37,7 @@ COUNTS = (0, 1, 3, 17)
 
 
 def load_emu():
-    h = C.CDLL(emu_build.build("smr_emu_web_view", "emu_web_view.cpp", ("smr_web_view.h", "smr_layout_dev.h", "smr_shader_dev.h", "smr_tables.h")))
+    h = C.CDLL(emu_build.build("smr_emu_web_view", "emu_web_view.cpp", ("smr_web_view.h", "smr_node_tiles.h", "../../tests/emu/emu_node_kernel.h", "smr_layout_dev.h", "smr_shader_dev.h", "smr_tables.h")))
     h.emu_web_view.argtypes = [P8, C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(P8), PI, PI, PF, C.c_int, C.c_int, C.c_uint32, C.c_uint32, P8, PU]
     h.emu_web_view.restype = C.c_int
     return h

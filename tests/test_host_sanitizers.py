@@ -12,58 +12,19 @@ import json
 import os
 import shutil
 import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
+from tests import san_build
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-HOST = os.path.join(ROOT, "smelter_amd", "csrc", "host")
-BUILD = os.path.join(HERE, "san", "_build")
-HOST_SOURCES = [os.path.join(HOST, f) for f in ("scene.cpp", "scene_build.cpp", "scene_capi.cpp", "text.cpp", "text_capi.cpp")]
-PROGRAMS = {  # executable -> its sources beyond HOST_SOURCES
-    "host_fuzz": [os.path.join(HERE, "san", "host_fuzz.cpp")],
-    "renderer_fuzz": [os.path.join(HERE, "san", "renderer_fuzz.cpp"), os.path.join(HERE, "san", "null_device.cpp"), os.path.join(HOST, "renderer.cpp")],
-}
-SOURCES = HOST_SOURCES + [p for v in PROGRAMS.values() for p in v]
-SANITIZE = "-fsanitize=address,undefined,float-cast-overflow"
-FLAGS = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", SANITIZE, "-fno-sanitize-recover=undefined,float-cast-overflow",
-         "-I", os.path.join(ROOT, "include"), "-I", HOST]
 FONT_DIRS = ["/usr/share/fonts/truetype/dejavu", os.path.join(HERE, "golden", "fonts")]
-
-
-def _newest_dependency():
-    deps = SOURCES + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".h")] + [os.path.join(ROOT, "include", "smr.h")]
-    return max(os.path.getmtime(p) for p in deps)
 
 
 @pytest.fixture(scope="module")
 def harness():
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("no g++")
-    os.makedirs(BUILD, exist_ok=True)
-    probe = os.path.join(BUILD, "probe.cpp")
-    with open(probe, "w") as f:
-        f.write("int main() { return 0; }\n")
-    if subprocess.run([gxx, SANITIZE, probe, "-o", os.path.join(BUILD, "probe")], capture_output=True).returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtimes")
-    exes = {name: os.path.join(BUILD, name) for name in PROGRAMS}
-    newest = _newest_dependency()
-    if all(os.path.exists(e) and os.path.getmtime(e) >= newest for e in exes.values()):
-        return exes
-
-    def compile_one(src):
-        obj = os.path.join(BUILD, os.path.basename(src) + ".o")
-        r = subprocess.run([gxx] + FLAGS + ["-c", src, "-o", obj], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        return obj
-    with ThreadPoolExecutor(max_workers=9) as ex:
-        objs = dict(zip(SOURCES, ex.map(compile_one, SOURCES)))
-    for name, own in PROGRAMS.items():
-        r = subprocess.run([gxx, SANITIZE] + [objs[p] for p in HOST_SOURCES + own] + ["-o", exes[name]], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-    return exes
+    return {"host_fuzz": san_build.build("host_fuzz", ("host_fuzz.cpp",)),
+            "renderer_fuzz": san_build.build("renderer_fuzz", ("renderer_fuzz.cpp", "null_device.cpp", "renderer.cpp"))}
 
 
 @pytest.fixture(scope="module")

@@ -105,7 +105,7 @@ def test_kernel_resources_tool_reads_a_user_shaders_code_object(programs, tmp_pa
 def test_registry_on_the_null_device_under_the_host_sanitizers(hip, tmp_path):
     """register source -> compile error -> registry unchanged; programs replaced and destroyed while registered elsewhere."""
     from smelter_amd import build
-    from tests import test_host_sanitizers as ths
+    from tests import san_build as ths
     gxx = shutil.which("g++")
     if not gxx:
         pytest.skip("no g++")

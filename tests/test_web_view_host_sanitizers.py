@@ -7,49 +7,16 @@ five entry points this feature reaches through weak references (staging of exact
 stream that is busy on request, smr_web_view).  The program is run directly."""
 import json
 import os
-import shutil
 import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-HOST = os.path.join(ROOT, "smelter_amd", "csrc", "host")
-BUILD = os.path.join(HERE, "san", "_build", "web_view")
-SOURCES = [os.path.join(HOST, f) for f in ("scene.cpp", "scene_build.cpp", "scene_capi.cpp", "text.cpp", "text_capi.cpp", "renderer.cpp")] + \
-    [os.path.join(HERE, "san", f) for f in ("null_device.cpp", "web_view_driver.cpp")]
-SANITIZE = "-fsanitize=address,undefined,float-cast-overflow"
-FLAGS = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", SANITIZE, "-fno-sanitize-recover=undefined,float-cast-overflow",
-         "-I", os.path.join(ROOT, "include"), "-I", HOST]
+from tests import san_build
 
 
 @pytest.fixture(scope="module")
 def driver():
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("no g++")
-    os.makedirs(BUILD, exist_ok=True)
-    probe = os.path.join(BUILD, "probe.cpp")
-    with open(probe, "w") as f:
-        f.write("int main() { return 0; }\n")
-    if subprocess.run([gxx, SANITIZE, probe, "-o", os.path.join(BUILD, "probe")], capture_output=True).returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtimes")
-    exe = os.path.join(BUILD, "web_view_driver")
-    deps = SOURCES + [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith(".h")] + [os.path.join(ROOT, "include", "smr.h")]
-    if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(p) for p in deps):
-        return exe
-
-    def compile_one(src):
-        obj = os.path.join(BUILD, os.path.basename(src) + ".o")
-        r = subprocess.run([gxx] + FLAGS + ["-c", src, "-o", obj], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        return obj
-    with ThreadPoolExecutor(max_workers=8) as ex:
-        objs = list(ex.map(compile_one, SOURCES))
-    r = subprocess.run([gxx, SANITIZE] + objs + ["-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return san_build.build("web_view_driver", ("renderer.cpp", "null_device.cpp", "web_view_driver.cpp"))
 
 
 def test_web_views_on_a_hostile_host_and_a_failing_device(driver):
