@@ -829,6 +829,23 @@ SMR_API int smr_renderer_set_text_measurer(smr_renderer *r, smr_text_measure_fn 
  * TextRendererNode::render does — in the node's colour over its background_color.  smr_renderer_set_text still replaces a node's run.
  * NULL detaches the book (and its measurer). */
 SMR_API int smr_renderer_set_fontbook(smr_renderer *r, smr_fontbook *book);
+/* Text nodes: cached rasters (with a font book).  What smr_renderer_update_scene draws of a Text node depends on the component alone, so the
+ * renderer keeps it: a raster is keyed by text, font_family, style, weight, wrap, align, font_size, line_height, the node's width x height,
+ * the text colour and the background colour (the scene's bytes) and the font book — a generation that smr_renderer_set_fontbook bumps,
+ * together with smr_fontbook_count — and shared by every node, output and lane that shows that key.
+ *   smr_renderer_update_scene: a node whose raster is resident points at it; every MISSING key is rasterised once (smr_fontbook_rasterise),
+ *     however many nodes share it, and all new rasters are drawn on the renderer's own context from ONE upload by ONE k_text_nodes launch
+ *     per 16 rasters and ONE synchronisation (each workgroup looks only at the glyphs that touch its 64 x 16 tile), in both rendering
+ *     modes.  An update that changes one label of forty rasterises, uploads and draws one.  A raster that no active scene of any output
+ *     shows after an update (or smr_renderer_unregister_output) is released, once frames in flight are done with it.
+ *   smr_renderer_set_text (the caller's own shaper): the node gets a surface of its OWN, never a cached one — a raster it shared stays as
+ *     it is for the other nodes —, drawn by the same kernel with one job.  After an update the caller supplies its runs again, as ever.
+ *   smr_renderer_set_fontbook: rasters made with the previous book are not reused; they go as their scenes are replaced.
+ *   smr_renderer_text_stats: smr_fontbook_rasterise calls so far, k_text_nodes launches so far (smr_renderer_set_text's included), rasters
+ *     resident now (no kernel counter slot, like smr_renderer_svg_stats).  Any out-pointer may be null.
+ * Hosts need change nothing: the pixels are those of one smr_blit_glyphs call per node, which is what the renderer made before.  Errors
+ * are as stated at smr_renderer_update_scene below.  Out of scope: glyph shapes and shaping; a device-resident glyph atlas across runs. */
+SMR_API int smr_renderer_text_stats(const smr_renderer *r, uint64_t *rasterise_calls, uint64_t *launches, uint32_t *resident);
 SMR_API int smr_renderer_set_text(smr_renderer *r, const char *output_id, int node, const float bg[4], const smr_glyph *glyphs, uint32_t n,
                                   const uint8_t *atlas_host, uint32_t atlas_w, uint32_t atlas_h);
 SMR_API int smr_renderer_render(smr_renderer *r, int64_t pts_ns, const smr_input_frame *inputs, uint32_t n_inputs,
@@ -879,7 +896,9 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      smr_renderer_web_positions, smr_renderer_web_launches, smr_web_rect, smr_web_embedding, SMR_NODE_WEB_VIEW = 5: a node kind no
  *      version-2 scene could produce — `web_view` was refused —, no struct changed, no kernel counter slot was added);
  *      SVG image assets and image unregistration (smr_svg_rasterise_fn, smr_renderer_register_svg_image, smr_renderer_unregister_image,
- *      smr_renderer_svg_stats: no struct changed, no kernel counter slot was added, no existing scene renders differently).
+ *      smr_renderer_svg_stats: no struct changed, no kernel counter slot was added, no existing scene renders differently);
+ *      the Text raster cache (smr_renderer_text_stats: no struct changed, no kernel counter slot was added, no existing scene renders
+ *      differently).
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

@@ -54,6 +54,7 @@ EXPORTS = [
     "smr_scene_register_web_renderer", "smr_renderer_register_web_renderer", "smr_renderer_unregister_web_renderer", "smr_renderer_web_paint",
     "smr_renderer_web_positions", "smr_renderer_web_launches",
     "smr_renderer_register_svg_image", "smr_renderer_unregister_image", "smr_renderer_svg_stats",
+    "smr_renderer_text_stats",
     "smr_abi_version", "smr_build_flags", "smr_sizeof_layout",
 ]
 NO_RESOLUTION = 0xFFFFFFFF
@@ -278,6 +279,7 @@ def load():
         "smr_renderer_register_svg_image": ([P, C.c_char_p, U, U, SVG_RASTERISE_FN, P], I),
         "smr_renderer_unregister_image": ([P, C.c_char_p], I),
         "smr_renderer_svg_stats": ([P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], I),
+        "smr_renderer_text_stats": ([P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], I),
         "smr_abi_version": ([], U),
         "smr_build_flags": ([], U),
         "smr_sizeof_layout": ([], U),

@@ -13,12 +13,14 @@
 // the root: owner_takes_the_roots_route below) has its raw planes moved to a root-resident frame by the same gather and is rendered exactly
 // as on one context.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <map>
 #include <set>
+#include <tuple>
 
 #include "scene.h"
 #include "shader_program.h"
@@ -47,6 +49,10 @@ extern "C" int smr_ctx_stream_idle(smr_ctx *ctx) __attribute__((weak));
 // The colour fix-up of new SVG rasters (k_svg_nodes, smr_convert.hip; not part of the ABI): n surfaces in place, one launch per 16.  Without
 // the GPU half the rasters keep the pixmap's bytes (nothing is drawn there either).
 extern "C" int smr_svg_nodes(smr_ctx *ctx, smr_surface *const *surfaces, uint32_t n) __attribute__((weak));
+// New Text rasters (k_text_nodes, smr_text_nodes.hip; not part of the ABI): n runs drawn from one upload by one launch per 16 and one
+// synchronisation.  Without the GPU half the renderer makes one smr_blit_glyphs call per run instead.
+extern "C" int smr_text_nodes(smr_ctx *ctx, smr_surface *const *targets, const float (*bg)[4], const smr_glyph *const *glyphs, const uint32_t *n_glyphs,
+                              const uint8_t *const *atlas_host, const uint32_t *atlas_w, const uint32_t *atlas_h, uint32_t n) __attribute__((weak));
 #pragma weak smr_host_alloc
 #pragma weak smr_host_free
 #pragma weak smr_frame_upload_async
@@ -134,6 +140,29 @@ struct ImageRes {
     bool svg() const { return svg_fn != nullptr; }
 };
 
+// What a Text node's raster depends on (with a font book: smr_renderer_update_scene draws the node itself): TextComponent's fields as
+// smr_fontbook_rasterise takes them, the node's size, both colours as the scene's bytes, and which font book — its generation (bumped by
+// smr_renderer_set_fontbook) and how many fonts it held when the raster was made.
+struct TextKey {
+    std::string text, family, style, weight, wrap, align;
+    float font_size = 0, line_height = 0;
+    uint32_t w = 0, h = 0;
+    uint8_t color[4] = {0, 0, 0, 0}, background[4] = {0, 0, 0, 0};
+    uint64_t book_generation = 0;
+    uint32_t book_fonts = 0;
+    auto tie() const {
+        return std::tie(w, h, font_size, line_height, book_generation, book_fonts, color[0], color[1], color[2], color[3], background[0], background[1],
+                        background[2], background[3], text, family, style, weight, wrap, align);
+    }
+    bool operator<(const TextKey &o) const { return tie() < o.tie(); }
+};
+// One resident Text raster: shared by every node, output and lane that shows the key; `refs` counts the (output, node) pairs of ACTIVE scenes
+// that point at it, and a raster nobody points at is released once frames in flight are done with it (release_unused_text).
+struct TextRaster {
+    smr_surface *surface = nullptr;
+    uint32_t refs = 0;
+};
+
 struct Source {
     uint32_t kind = SMR_SOURCE_NONE;
     const smr_surface *surface = nullptr;
@@ -204,7 +233,9 @@ struct Output {
     uint32_t w = 0, h = 0, format = SMR_FRAME_PLANAR_YUV420;
     std::deque<OutputLane> lanes;              // one per renderer lane, grown on demand (a deque: callers hold pointers to `frames`)
     OutputLane *l = nullptr;                   // the lane of the frame being rendered
-    std::vector<smr_surface *> text_surface;   // per graph node: the rendered glyph run of a Text node (once per scene update; read-only per frame)
+    std::vector<smr_surface *> text_surface;   // per graph node: the rendered glyph run of a Text node (read-only per frame) — a cached raster's
+                                               // surface, borrowed (text_raster[node] names it), or the node's own (smr_renderer_set_text)
+    std::vector<TextRaster *> text_raster;     // per graph node: the cached raster text_surface[node] is borrowed from, or null
 };
 
 }  // namespace
@@ -235,6 +266,9 @@ struct smr_renderer {
     std::map<std::string, WebInstance> web;   // smr_renderer_register_web_renderer
     uint64_t web_launches = 0;        // smr_renderer_web_launches
     uint64_t svg_calls = 0, svg_launches = 0;  // smr_renderer_svg_stats
+    std::map<TextKey, TextRaster> text_rasters;    // the Text raster cache (std::map: the nodes' pointers to its values stay valid)
+    uint64_t fontbook_generation = 0;              // smr_renderer_set_fontbook calls so far
+    uint64_t text_calls = 0, text_launches = 0;    // smr_renderer_text_stats
     size_t lane = 0;                  // the lane of the frame being rendered (index into lane_ctx)
 };
 
@@ -286,8 +320,13 @@ void free_node_surfaces(smr_renderer *r, Output &o) {
         l.scaled_image.assign(n, nullptr);
         l.image_drawn.assign(n, 0);
     }
-    free_surfaces(r, o.text_surface);
+    // Text: a borrowed raster loses a reference (release_unused_text lets it go when nobody is left), a node's own surface is destroyed
+    for (size_t i = 0; i < o.text_surface.size(); i++) {
+        if (i < o.text_raster.size() && o.text_raster[i]) o.text_raster[i]->refs--;
+        else if (o.text_surface[i]) smr_surface_destroy(r->ctx, o.text_surface[i]);
+    }
     o.text_surface.assign(n, nullptr);
+    o.text_raster.assign(n, nullptr);
 }
 void free_output(smr_renderer *r, Output &o) {
     free_node_surfaces(r, o);
@@ -399,6 +438,35 @@ void release_unused_rasters(smr_renderer *r) {
             it = rasters.erase(it);
         }
     }
+}
+
+// ---- the Text raster cache
+// Rasters no node of an active scene points at any more.  (Callers have synchronised every context: frames in flight may still sample them.)
+void release_unused_text(smr_renderer *r) {
+    for (auto it = r->text_rasters.begin(); it != r->text_rasters.end();) {
+        if (it->second.refs) { ++it; continue; }
+        smr_surface_destroy(r->lane_ctx[0], it->second.surface);
+        it = r->text_rasters.erase(it);
+    }
+}
+// Draws n runs into n surfaces on the renderer's own context: ONE smr_text_nodes call (one upload, one launch per 16, one synchronisation;
+// every lane's stream may read the surfaces afterwards), or, without the GPU half, one smr_blit_glyphs call per run.
+int draw_text_runs(smr_renderer *r, smr_surface *const *targets, const float (*bg)[4], const smr_glyph *const *glyphs, const uint32_t *n_glyphs,
+                   const uint8_t *const *atlas, const uint32_t *atlas_w, const uint32_t *atlas_h, uint32_t n) {
+    if (!n) return 0;
+    smr_ctx *c = r->lane_ctx[0];
+    if (smr_text_nodes) {
+        const int rc = smr_text_nodes(c, targets, bg, glyphs, n_glyphs, atlas, atlas_w, atlas_h, n);
+        if (rc < 0) return fail(r, rc, std::string("text node: ") + smr_last_error(c));
+        r->text_launches += (n + 15) / 16;
+        return 0;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const int rc = smr_blit_glyphs(c, targets[i], bg[i], glyphs[i], n_glyphs[i], atlas[i], atlas_w[i], atlas_h[i]);
+        if (rc < 0) return fail(r, rc, std::string("text node: ") + smr_last_error(c));
+        r->text_launches++;
+    }
+    return 0;
 }
 
 // One pixmap on its way to a raster: what the rasteriser filled, and the surface it is uploaded into
@@ -972,6 +1040,29 @@ int smr_renderer_register_shader_hook(smr_renderer *r, const char *shader_id, co
     return 0;
 }
 int smr_renderer_fail(smr_renderer *r, int code, const std::string &msg) { return fail(r, code, msg); }
+// The Text raster cache's bookkeeping, recounted (tests/san/text_bins_driver.cpp; not exported): 0 when every raster's `refs` is the number
+// of (output, node) pairs that point at it, every such pointer is a resident raster whose surface the node shows, and no raster is
+// resident without a reference; else -1.
+int smr_renderer_text_cache_check(const smr_renderer *r) {
+    std::map<const TextRaster *, uint32_t> seen;
+    for (const auto &kv : r->text_rasters) {
+        if (!kv.second.surface || !kv.second.refs) return -1;
+        seen[&kv.second] = 0;
+    }
+    for (const auto &kv : r->outputs) {
+        const Output &o = kv.second;
+        if (o.text_raster.size() != o.text_surface.size()) return -1;
+        for (size_t i = 0; i < o.text_raster.size(); i++) {
+            if (!o.text_raster[i]) continue;
+            auto it = seen.find(o.text_raster[i]);
+            if (it == seen.end() || o.text_surface[i] != o.text_raster[i]->surface) return -1;
+            it->second++;
+        }
+    }
+    for (const auto &kv : seen)
+        if (kv.second != kv.first->refs) return -1;
+    return 0;
+}
 
 extern "C" {
 
@@ -990,6 +1081,7 @@ SMR_API void smr_renderer_destroy(smr_renderer *r) {
     if (!r) return;
     sync_lanes(r);
     for (auto &kv : r->outputs) free_output(r, kv.second);
+    release_unused_text(r);  // (every output is gone: every Text raster)
     for (auto &kv : r->images) free_image(r, kv.second);  // (resident SVG rasters included)
     for (auto &kv : r->web) free_web_instance(r, kv.second);  // (paints nobody rendered included)
     if (r->comm) smr_comm_destroy(r->comm);
@@ -1130,6 +1222,14 @@ SMR_API int smr_renderer_svg_stats(const smr_renderer *r, uint64_t *rasterise_ca
     return 0;
 }
 
+SMR_API int smr_renderer_text_stats(const smr_renderer *r, uint64_t *rasterise_calls, uint64_t *launches, uint32_t *resident) {
+    if (!r) return -1;
+    if (rasterise_calls) *rasterise_calls = r->text_calls;
+    if (launches) *launches = r->text_launches;
+    if (resident) *resident = (uint32_t)r->text_rasters.size();
+    return 0;
+}
+
 // WebRenderer::new (web_renderer/renderer.rs:43-76) without the browser: the spec's resolution and embedding method
 SMR_API int smr_renderer_register_web_renderer(smr_renderer *r, const char *instance_id, uint32_t width, uint32_t height, uint32_t embedding) {
     if (!r || !instance_id) return fail(r, -1, "smr_renderer_register_web_renderer: null argument");
@@ -1200,6 +1300,7 @@ SMR_API int smr_renderer_set_text_measurer(smr_renderer *r, smr_text_measure_fn 
 SMR_API int smr_renderer_set_fontbook(smr_renderer *r, smr_fontbook *book) {
     if (!r) return -1;
     r->fontbook = book;
+    r->fontbook_generation++;  // (Text rasters made with the previous book are no longer found: TextKey)
     r->measure = book ? smr_fontbook_measure : nullptr;
     r->measure_user = book;
     for (auto &kv : r->outputs) kv.second.scene.set_text_measurer(r->measure, r->measure_user);
@@ -1215,30 +1316,73 @@ SMR_API int smr_renderer_register_shader(smr_renderer *r, const char *shader_id,
     return 0;
 }
 
-// TextRendererNode::render for one node (text_renderer.rs:72-167): clear to the background colour, blit the glyph run — once per update
+// TextRendererNode::render for one node with the caller's own run (text_renderer.rs:72-167): clear to the background colour, blend the glyph
+// run — into a surface of the node's OWN, never a cached raster: a raster the node borrowed so far goes back to the cache (and is released
+// when no other node shows it).
 static int set_text_run(smr_renderer *r, Output &o, int node, const float bg[4], const smr_glyph *glyphs, uint32_t n, const uint8_t *atlas,
                         uint32_t atlas_w, uint32_t atlas_h) {
     const Stateful &c = *o.scene.nodes()[node].component;
     const uint32_t w = as_u32(c.leaf_size.width), h = as_u32(c.leaf_size.height);
     if (!w || !h) return 0;  // (a zero-sized text node is the 1x1 transparent texture: text_renderer.rs:77-85)
+    if (o.text_raster[node]) {
+        TextRaster *shared = o.text_raster[node];
+        o.text_raster[node] = nullptr;
+        o.text_surface[node] = nullptr;
+        if (--shared->refs == 0) {
+            sync_lanes(r);  // frames in flight may still sample it
+            release_unused_text(r);
+        }
+    }
     int rc = ensure_surface(r, o.text_surface[node], w, h);
     if (rc < 0) return rc;
-    rc = gpu(r, smr_blit_glyphs(r->ctx, o.text_surface[node], bg, glyphs, n, atlas, atlas_w, atlas_h), "text node");
-    // every lane's stream reads the run from its next frame on
-    if (rc >= 0 && r->lane_ctx.size() > 1) rc = gpu(r, smr_sync(r->ctx), "text node");
-    return rc;
+    // (smr_text_nodes / smr_blit_glyphs return synchronised: every lane's stream reads the run from its next frame on)
+    smr_surface *const target = o.text_surface[node];
+    const float (*bgs)[4] = (const float (*)[4])bg;
+    return draw_text_runs(r, &target, bgs, &glyphs, &n, &atlas, &atlas_w, &atlas_h, 1);
 }
 
 // With a font book the renderer is its own TextRendererCtx: every Text node of the new scene is laid out at its resolved size
 // (layout_text's final set_size: the node's width, text_renderer.rs:333-343), rasterised and drawn — in TextComponent's colour
-// (glyphon::Color::rgba of the straight bytes, text_renderer.rs:176-177) over convert_to_shader_color(background_color) (:62, 371-374).
-static int draw_text_nodes(smr_renderer *r, const std::string &output_id, Output &o) {
-    (void)output_id;
+// (glyphon::Color::rgba of the straight bytes, text_renderer.rs:176-177) over convert_to_shader_color(background_color) (:62, 371-374) —
+// ONCE PER KEY (TextKey), not once per node and update: a node whose raster is resident points at it, every missing key is rasterised once
+// however many nodes share it, and all new rasters are drawn by one draw_text_runs call.  (The caller has dropped the replaced scene's
+// references, free_node_surfaces, and releases what nobody points at afterwards: a raster both scenes show is simply found again.)
+static int draw_text_nodes(smr_renderer *r, Output &o) {
     const auto &nodes = o.scene.nodes();
+    struct Pending {
+        TextKey key;
+        std::vector<int> nodes;
+        float bg[4];
+        std::vector<smr_glyph> glyphs;  // (a font book's run lives until its next rasterise call: copied)
+        std::vector<uint8_t> atlas;
+        uint32_t atlas_w = 0, atlas_h = 0;
+        smr_surface *surface = nullptr;
+    };
+    std::vector<Pending> pend;
+    const bool srgb = smr_ctx_mode(r->lane_ctx[0]) == SMR_MODE_GPU_OPTIMIZED;
     for (int i = 0; i < (int)nodes.size(); i++) {
         if (nodes[i].kind != Kind::Text) continue;
         const Stateful &c = *nodes[i].component;
         const Stateful::TextSpec &t = c.text_spec;
+        TextKey k;
+        k.text = c.text; k.family = t.family; k.style = t.style; k.weight = t.weight; k.wrap = t.wrap; k.align = t.align;
+        k.font_size = t.font_size; k.line_height = t.line_height;
+        k.w = as_u32(c.leaf_size.width); k.h = as_u32(c.leaf_size.height);
+        k.color[0] = t.color.r; k.color[1] = t.color.g; k.color[2] = t.color.b; k.color[3] = t.color.a;
+        k.background[0] = t.background.r; k.background[1] = t.background.g; k.background[2] = t.background.b; k.background[3] = t.background.a;
+        k.book_generation = r->fontbook_generation; k.book_fonts = smr_fontbook_count(r->fontbook);
+        if (!k.w || !k.h) continue;  // (a zero-sized text node is the 1x1 transparent texture: text_renderer.rs:77-85)
+        auto hit = r->text_rasters.find(k);
+        if (hit != r->text_rasters.end()) {
+            hit->second.refs++;
+            o.text_raster[i] = &hit->second;
+            o.text_surface[i] = hit->second.surface;
+            continue;
+        }
+        bool queued = false;
+        for (Pending &p : pend)
+            if (!queued && !(p.key < k) && !(k < p.key)) { p.nodes.push_back(i); queued = true; }
+        if (queued) continue;
         smr_text_params p;
         memset(&p, 0, sizeof(p));
         p.text = c.text.c_str(); p.font_family = t.family.c_str(); p.style = t.style.c_str(); p.weight = t.weight.c_str(); p.wrap = t.wrap.c_str();
@@ -1246,15 +1390,52 @@ static int draw_text_nodes(smr_renderer *r, const std::string &output_id, Output
         p.font_size = t.font_size; p.line_height = t.line_height;
         p.max_width = c.leaf_size.width; p.max_height = c.leaf_size.height;
         const float color[4] = {t.color.r / 255.0f, t.color.g / 255.0f, t.color.b / 255.0f, t.color.a / 255.0f};
-        float bg[4];
-        convert_to_shader_color(t.background, smr_ctx_mode(r->ctx) == SMR_MODE_GPU_OPTIMIZED, bg);
         smr_text_run run;
-        if (smr_fontbook_rasterise(r->fontbook, &p, as_u32(c.leaf_size.width), as_u32(c.leaf_size.height), color, &run) != 0)
+        r->text_calls++;
+        if (smr_fontbook_rasterise(r->fontbook, &p, k.w, k.h, color, &run) != 0)
             return fail(r, -1, std::string("text node: ") + smr_fontbook_last_error(r->fontbook));
-        const int rc = set_text_run(r, o, i, bg, run.glyphs, run.n_glyphs, run.atlas, run.atlas_w, run.atlas_h);
-        if (rc < 0) return rc;
+        pend.emplace_back();
+        Pending &q = pend.back();
+        q.key = k;
+        q.nodes.push_back(i);
+        convert_to_shader_color(t.background, srgb, q.bg);
+        if (run.n_glyphs) {
+            q.glyphs.assign(run.glyphs, run.glyphs + run.n_glyphs);
+            q.atlas.assign(run.atlas, run.atlas + (size_t)run.atlas_w * run.atlas_h);
+        }
+        q.atlas_w = run.atlas_w; q.atlas_h = run.atlas_h;
     }
-    return 0;
+    // the new rasters' surfaces: what cannot be made leaves its nodes transparent (include/smr.h), the rest is drawn
+    int rc = 0;
+    std::vector<smr_surface *> targets;
+    std::vector<std::array<float, 4>> bgs;
+    std::vector<const smr_glyph *> glyphs;
+    std::vector<const uint8_t *> atlases;
+    std::vector<uint32_t> counts, aw, ah;
+    std::vector<Pending *> made;
+    for (Pending &q : pend) {
+        const int e = gpu(r, smr_surface_create(r->lane_ctx[0], q.key.w, q.key.h, SMR_PX_RGBA8, &q.surface), "text node");
+        if (e < 0) { q.surface = nullptr; rc = e; break; }
+        made.push_back(&q);
+        targets.push_back(q.surface);
+        bgs.push_back({q.bg[0], q.bg[1], q.bg[2], q.bg[3]});
+        glyphs.push_back(q.glyphs.data()); counts.push_back((uint32_t)q.glyphs.size());
+        atlases.push_back(q.atlas.data()); aw.push_back(q.atlas_w); ah.push_back(q.atlas_h);
+    }
+    const int drawn = draw_text_runs(r, targets.data(), (const float (*)[4])bgs.data(), glyphs.data(), counts.data(), atlases.data(), aw.data(), ah.data(),
+                                     (uint32_t)targets.size());
+    if (drawn < 0) {  // (nothing of this update's rasters is kept: their nodes render transparent)
+        (void)smr_sync(r->lane_ctx[0]);
+        for (Pending *q : made) smr_surface_destroy(r->lane_ctx[0], q->surface);
+        return drawn;
+    }
+    for (Pending *q : made) {
+        TextRaster &ra = r->text_rasters[q->key];
+        ra.surface = q->surface;
+        ra.refs = (uint32_t)q->nodes.size();
+        for (int i : q->nodes) { o.text_raster[i] = &ra; o.text_surface[i] = ra.surface; }
+    }
+    return rc;
 }
 
 SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, uint32_t width, uint32_t height, uint32_t output_format,
@@ -1357,7 +1538,10 @@ SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, ui
     int rc = enter_lane(r, o, 0);  // the output's first frames exist after a successful update, as before
     // (what is left to fail below is a device allocation — the frames, a text node's surface: SMR_ERR_OOM with the NEW scene active and the
     //  nodes that could not be drawn transparent; include/smr.h says so.  Everything the scene itself can get wrong was refused above.)
-    if (rc >= 0 && r->fontbook) rc = draw_text_nodes(r, output_id, o);
+    // (Text rasters: the new scene's are found or made first, then those only the replaced scene showed go — every context is idle since
+    //  sync_lanes above, and smr_text_nodes returns synchronised)
+    if (rc >= 0 && r->fontbook) rc = draw_text_nodes(r, o);
+    release_unused_text(r);
     return rc;
 }
 
@@ -1369,6 +1553,7 @@ SMR_API int smr_renderer_unregister_output(smr_renderer *r, const char *output_i
     free_output(r, it->second);
     r->outputs.erase(it);
     release_unused_rasters(r);
+    release_unused_text(r);
     return 0;
 }
 

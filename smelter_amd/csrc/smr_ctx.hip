@@ -199,6 +199,7 @@ void smr_ctx_destroy(smr_ctx *ctx) {
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
     for (auto &s : ctx->scratch)
         if (s.ptr) (void)hipFree(s.ptr);
+    if (ctx->text_host) (void)hipHostFree(ctx->text_host);
     for (auto *s : ctx->surf_cache)
         if (s) smr_surface_destroy(ctx, s);
     for (auto &t : ctx->weight_tables)

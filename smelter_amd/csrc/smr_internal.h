@@ -161,6 +161,8 @@ struct smr_ctx {
     // scratch owned by the ctx (resampler intermediates, fused tiles)
     struct Scratch { void *ptr = nullptr; size_t bytes = 0; };
     std::vector<Scratch> scratch;  // indexed slots, grown on demand
+    void *text_host = nullptr;     // smr_text_nodes' pinned block (records, bins and atlases of one call), grown on demand
+    size_t text_host_bytes = 0;
 
     // size-keyed reusable surfaces (NodeTexture::ensure_size, state/node_texture.rs:22-42)
     std::vector<smr_surface *> surf_cache;

@@ -6,6 +6,7 @@
 // (transformations/shader/node.rs:71-89) for the library's built-in kernels.  A user's own
 // shader, written in HIP C++, goes through smr_user_shader.hip (WGSL text: no naga->HIP compiler).
 #include "smr_internal.h"
+#include "smr_text_nodes.h"
 
 #include <cmath>
 
@@ -36,20 +37,9 @@ __global__ __launch_bounds__(256) void k_blit_glyphs(SurfView target, float4 bg,
         const smr_glyph &gl = glyphs[i];
         const int gx = x - gl.dst_x, gy = y - gl.dst_y;
         if (gx < 0 || gy < 0 || gx >= gl.w || gy >= gl.h) continue;
-        const float cov = (float)atlas[(size_t)(gl.atlas_y + gy) * aw + (gl.atlas_x + gx)] / 255.0f;
-        const float al = gl.color[3] * cov;
-        const float inv = 1.0f - al;
         const float4 col = glyph_rgb[i];
-        if (srgb) {
-            r = srgb_encode8(col.x * al + dec[r] * inv, thr);
-            g = srgb_encode8(col.y * al + dec[g] * inv, thr);
-            b = srgb_encode8(col.z * al + dec[b] * inv, thr);
-        } else {
-            r = unorm8(col.x * al + ((float)r / 255.0f) * inv);
-            g = unorm8(col.y * al + ((float)g / 255.0f) * inv);
-            b = unorm8(col.z * al + ((float)b / 255.0f) * inv);
-        }
-        a = unorm8(al + ((float)a / 255.0f) * inv);
+        // (the blend is stated once, in smr_text_nodes.h: k_text_nodes is held to this kernel byte for byte)
+        tx_blend_glyph(r, g, b, a, atlas[(size_t)(gl.atlas_y + gy) * aw + (gl.atlas_x + gx)], col.x, col.y, col.z, gl.color[3], srgb, dec, thr);
     }
     *(u32 *)(target.ptr + (size_t)y * target.pitch + (size_t)x * 4) = r | (g << 8) | (b << 16) | (a << 24);
 }
@@ -104,11 +94,6 @@ void launch_gauss_axis(smr_ctx *ctx, const SurfView &src, const SurfView &dst, f
     hipLaunchKernelGGL((k_gauss_axis<BW, BH, AXIS>), grid, dim3(256), lds, ctx->stream, src, dst, sigma, radius, pxi, ctx->d_tables);
 }
 
-double srgb_to_linear_f64(double c) {
-    if (c < 0.04045) return c / 12.92;
-    return pow((c + 0.055) / 1.055, 2.4);
-}
-
 }  // namespace
 
 extern "C" {
@@ -118,11 +103,7 @@ int smr_blit_glyphs(smr_ctx *ctx, smr_surface *target, const float bg[4], const 
     SMR_ENTER(ctx);
     if (!ctx || !target || !bg || (n && (!glyphs || !atlas_host))) return SMR_ERR_INVALID;
     if (target->fmt != SMR_PX_RGBA8) return smr_fail(ctx, SMR_ERR_INVALID, "smr_blit_glyphs: target must be RGBA8");
-    for (u32 i = 0; i < n; i++) {
-        const smr_glyph &g = glyphs[i];
-        if (g.w < 0 || g.h < 0 || g.atlas_x < 0 || g.atlas_y < 0 || (u32)(g.atlas_x + g.w) > atlas_w || (u32)(g.atlas_y + g.h) > atlas_h)
-            return smr_fail(ctx, SMR_ERR_INVALID, "smr_blit_glyphs: glyph %u reads outside the %ux%u atlas", i, atlas_w, atlas_h);
-    }
+    if (const int rc = tx_check_glyphs(ctx, "smr_blit_glyphs", glyphs, n, atlas_w, atlas_h)) return rc;
     // Text nodes render once per scene update (text_renderer.rs:73-75,166): a blocking upload is fine here.
     const size_t g_bytes = ((size_t)n * sizeof(smr_glyph) + 255) & ~(size_t)255;
     const size_t c_bytes = ((size_t)n * sizeof(float4) + 255) & ~(size_t)255;
@@ -132,11 +113,7 @@ int smr_blit_glyphs(smr_ctx *ctx, smr_surface *target, const float bg[4], const 
     std::vector<float4> cols(n ? n : 1);
     for (u32 i = 0; i < n; i++) {
         float c[3];
-        for (int k = 0; k < 3; k++) {
-            float v = glyphs[i].color[k];
-            v = !(v > 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v);
-            c[k] = ctx->srgb() ? (float)srgb_to_linear_f64((double)v) : v;
-        }
+        tx_glyph_colour(ctx->srgb(), glyphs[i], c);
         cols[i] = make_float4(c[0], c[1], c[2], 0.0f);
     }
     if (n) {

@@ -148,6 +148,12 @@ class Renderer:
         self._check(self.lib.smr_renderer_svg_stats(self._h, C.byref(calls), C.byref(launches), C.byref(resident)))
         return calls.value, launches.value, resident.value
 
+    def text_stats(self) -> Tuple[int, int, int]:
+        """(smr_fontbook_rasterise calls so far, k_text_nodes launches so far, Text rasters resident now) (smr_renderer_text_stats)."""
+        calls, launches, resident = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self._check(self.lib.smr_renderer_text_stats(self._h, C.byref(calls), C.byref(launches), C.byref(resident)))
+        return calls.value, launches.value, resident.value
+
     # -- WebView nodes: the browser is the caller's, the node's compositing is the library's (include/smr.h, "WebView nodes")
     def register_web_renderer(self, instance_id: str, width: int, height: int, embedding: int = _ffi.WEB_NATIVE_OVER_CONTENT):
         """A web renderer instance of width x height; `embedding`: _ffi.WEB_CHROMIUM_EMBEDDING / WEB_NATIVE_OVER_CONTENT /
