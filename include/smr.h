@@ -55,6 +55,8 @@ typedef enum smr_pixel_format {
     SMR_PX_RGBA16F = 1, /* resampler intermediate (layout/resampler.rs:25-28)       */
     SMR_PX_R8 = 2,      /* Y / U / V plane (wgpu/texture/planar_yuv.rs:111-129)     */
     SMR_PX_RG8 = 3,     /* NV12 chroma plane (wgpu/texture/nv12.rs)                 */
+    SMR_PX_R16 = 4,     /* one little-endian 16-bit word per texel: a 10-bit Y / U / V plane, the Y plane of P010 */
+    SMR_PX_RG16 = 5,    /* two words per texel: the U V plane of P010                */
 } smr_pixel_format;
 
 /* smelter-render/src/types.rs:27-40 FrameData */
@@ -69,10 +71,19 @@ typedef enum smr_frame_format {
     SMR_FRAME_BGRA = 7,
     SMR_FRAME_ARGB = 8,
     SMR_FRAME_RGBA = 9, /* Rgba8UnormWgpuTexture: straight alpha, premultiplied on ingest */
+    /* 10-bit 4:2:0, what HEVC Main10 / AV1 / VP9 profile 2 decoders hand over (no FrameData variant: the reference has no 10-bit path).
+     * Limited range, opaque, INPUT ONLY: smr_rgba_to_frame, smr_frame_fill_black and a renderer's output_format refuse them.
+     * A 10-bit code c is the 8-bit code c / 4 with two more fractional bits: its unorm value is (c * 0.25) / 255, and from there on the
+     * conversion is planar_yuv_to_rgba.wgsl / nv12_to_rgba.wgsl unchanged (limited range 64 .. 940 is exactly 16 .. 235) — a frame whose
+     * codes are 4 b has, byte for byte, the node texture of the 8-bit frame with bytes b.
+     * Not offered: full-range 10-bit, 4:2:2 / 4:4:4 10-bit (P210, Y210), 12-bit, 10-bit outputs, and these formats on the plane-source
+     * route (SMR_OPT_PLANE_SOURCE) or the laboratory fused conversion — both keep rejecting the formats they do not name. */
+    SMR_FRAME_P010 = 10,              /* {Y: R16 w x h, UV: RG16 w/2 x h/2}; code = word >> 6, the low six bits are ignored */
+    SMR_FRAME_PLANAR_YUV420P10 = 11,  /* {Y, U, V}, all R16; code = word & 0x3ff, the high six bits are ignored */
 } smr_frame_format;
 
 /* One video frame resident in HBM: up to three pitched plane surfaces.
- * planes[] per format: planar YUV {Y,U,V}; NV12 {Y (R8), UV (RG8)}; packed formats {data}.
+ * planes[] per format: planar YUV {Y,U,V}; NV12 {Y (R8), UV (RG8)}; P010 {Y (R16), UV (RG16)}; planar 10-bit {Y,U,V} (R16); packed formats {data}.
  * UYVY/YUYV planes are RGBA8 surfaces of width/2 texels (wgpu/texture/interleaved_yuv422.rs). */
 typedef struct smr_frame {
     uint32_t format; /* smr_frame_format */
@@ -898,7 +909,9 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      SVG image assets and image unregistration (smr_svg_rasterise_fn, smr_renderer_register_svg_image, smr_renderer_unregister_image,
  *      smr_renderer_svg_stats: no struct changed, no kernel counter slot was added, no existing scene renders differently);
  *      the Text raster cache (smr_renderer_text_stats: no struct changed, no kernel counter slot was added, no existing scene renders
- *      differently).
+ *      differently);
+ *      10-bit 4:2:0 input frames (SMR_PX_R16, SMR_PX_RG16, SMR_FRAME_P010, SMR_FRAME_PLANAR_YUV420P10: input only, no struct changed, no
+ *      kernel counter slot was added, no 8-bit frame converts differently).
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

@@ -14,8 +14,10 @@ LIB_PATH = os.environ.get("SMR_LIB") or os.path.join(_HERE, "libsmr_hip.so")  # 
 SMR_OK, SMR_ERR_INVALID, SMR_ERR_OOM, SMR_ERR_INTERNAL = 0, -1, -2, -3
 MODE_GPU_OPTIMIZED, MODE_CPU_OPTIMIZED = 0, 1
 PX_RGBA8, PX_RGBA16F, PX_R8, PX_RG8 = 0, 1, 2, 3
+PX_R16, PX_RG16 = 4, 5  # 16-bit words: the planes of the 10-bit frame formats
 (FRAME_PLANAR_YUV420, FRAME_PLANAR_YUV422, FRAME_PLANAR_YUV444, FRAME_PLANAR_YUVJ420, FRAME_UYVY422, FRAME_YUYV422,
  FRAME_NV12, FRAME_BGRA, FRAME_ARGB, FRAME_RGBA) = range(10)
+FRAME_P010, FRAME_PLANAR_YUV420P10 = 10, 11  # 10-bit 4:2:0, limited range, input only (code = word >> 6 | word & 0x3ff)
 MAX_MASKS = 20
 NO_SOURCE = 0xFFFFFFFF
 SOURCE_NONE, SOURCE_SURFACE, SOURCE_FRAME, SOURCE_OPAQUE_SURFACE = 0, 1, 2, 3

@@ -22,6 +22,7 @@
 #include <set>
 #include <tuple>
 
+#include "../smr_frame_formats.h"  // (beside smr_internal.h, which needs HIP; this one does not)
 #include "scene.h"
 #include "shader_program.h"
 
@@ -175,7 +176,7 @@ struct Source {
 };
 
 // every YUV-family FrameData variant converts to alpha == 1 (wgpu/format/*_to_rgba.wgsl return vec4(.., 1.0)); BGRA / ARGB / RGBA carry their own
-bool frame_opaque(const smr_frame *f) { return f && f->format <= SMR_FRAME_NV12; }
+bool frame_opaque(const smr_frame *f) { return f && frame_format_is_opaque_ycbcr(f->format); }
 
 // Does a LayoutNode's output have alpha 255 everywhere?  Yes when one of its layers is opaque — a colour with alpha 1, a texture whose source
 // is opaque: bilinear weights are 8-bit fractions and sum to 1 exactly, so an opaque texture samples alpha exactly 1 —, has no rotation, rounded
@@ -1443,7 +1444,8 @@ SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, ui
     if (!r || !output_id || !scene_json || !width || !height) return fail(r, -1, "smr_renderer_update_scene: null argument");
     if (output_format != SMR_FRAME_PLANAR_YUV420 && output_format != SMR_FRAME_PLANAR_YUV422 && output_format != SMR_FRAME_PLANAR_YUV444 &&
         output_format != SMR_FRAME_NV12 && output_format != SMR_FRAME_RGBA)
-        return fail(r, -1, "smr_renderer_update_scene: output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12 or RGBA");
+        return fail(r, -1, frame_format_is_hi_depth(output_format) ? "smr_renderer_update_scene: the 10-bit frame formats are input only; output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12 or RGBA"
+                                                                   : "smr_renderer_update_scene: output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12 or RGBA");
     Output &o = r->outputs[output_id];
     for (auto &kv : r->images) o.scene.register_image(kv.first, (float)kv.second.w, (float)kv.second.h);
     for (auto &kv : r->web) o.scene.register_web_renderer(kv.first, (float)kv.second.w, (float)kv.second.h);

@@ -11,6 +11,7 @@
 // on a fresh cache line.
 #include "smr_convert_dev.h"
 #include "smr_convert_420.h"
+#include "smr_convert_hi.h"
 #include "smr_svg_nodes.h"
 
 namespace {
@@ -42,6 +43,41 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up,
             vv = sample_plane_bilinear(up, 2, 1, tu, tv);
         }
         px[i] = yuv_to_rgb_px(yy, uu, vv, full != 0);
+    }
+    u8 *row = dst.ptr + (size_t)y * dst.pitch;
+    if (x0 + 3 < dst.w) {
+        *(uint4 *)(row + (size_t)x0 * 4) = make_uint4(px[0], px[1], px[2], px[3]);
+    } else {
+        for (int i = 0; i < 4 && x0 + i < dst.w; i++) *(u32 *)(row + (size_t)(x0 + i) * 4) = px[i];
+    }
+}
+
+// The 10-bit twin (smr_convert_hi.h), statement for statement with the 16-bit fetch: any geometry — odd sizes, widths below 8, 1x1 with
+// placeholder chroma planes.  kind: 0 planar 10-bit (3 R16 planes, code = word & 0x3ff), 1 P010 (R16 + RG16, code = word >> 6); limited range.
+template <int KIND>
+__global__ __launch_bounds__(BLOCK) void k_yuv_hi_to_rgba(SurfView yp, SurfView up, SurfView vp, SurfView dst) {
+    const int groups = (dst.w + 3) >> 2;
+    const int gx = blockIdx.x * BLOCK + threadIdx.x;
+    const int y = blockIdx.y;
+    if (gx >= groups) return;
+    const int x0 = gx * 4;
+    const float tv = ((float)y + 0.5f) / (float)dst.h;
+    u32 px[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        int x = x0 + i;
+        if (x >= dst.w) { px[i] = 0; continue; }
+        float tu = ((float)x + 0.5f) / (float)dst.w;
+        float yy = cvhi_fetch<KIND == 1>(yp.ptr + (size_t)y * yp.pitch, x);
+        float uu, vv;
+        if (KIND == 0) {
+            uu = sample_plane_bilinear_hi<false>(up, 1, 0, tu, tv);
+            vv = sample_plane_bilinear_hi<false>(vp, 1, 0, tu, tv);
+        } else {
+            uu = sample_plane_bilinear_hi<true>(up, 2, 0, tu, tv);
+            vv = sample_plane_bilinear_hi<true>(up, 2, 1, tu, tv);
+        }
+        px[i] = yuv_to_rgb_px(yy, uu, vv, false);
     }
     u8 *row = dst.ptr + (size_t)y * dst.pitch;
     if (x0 + 3 < dst.w) {
@@ -406,6 +442,17 @@ __global__ __launch_bounds__(BLOCK) void k_yuv420_to_rgba_tight(const ConvBatch 
 #endif
 }
 
+// 10-bit 4:2:0 frames the block converter takes (smr_convert_hi.h, conv_hi_mode): the same persistent launch cut into equal shares, with two
+// 1024-entry tables (the code's unorm value, its luma range expansion) built per workgroup with the operations themselves — 8 KB of LDS, the four
+// workgroups a CU holds at 101 registers stay far below its 160 KB.  One kernel per format, no plain / tight pair: no load leaves a plane row's bytes.
+template <bool P010>
+__global__ __launch_bounds__(BLOCK) void k_yuv420_hi_to_rgba(const ConvBatch B) {
+    __shared__ float s_ylut[CVHI_CODES], s_ulut[CVHI_CODES];
+    cvhi_build_tables(s_ylut, s_ulut, threadIdx.x, BLOCK);
+    __syncthreads();
+    cvhi_share<P010>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, threadIdx.x & 63u, s_ylut, s_ulut);
+}
+
 // rgba_to_yuv.wgsl's three passes (k_rgba_to_y + k_rgba_to_chroma) in one launch for even-sized frames: a thread owns a 4 x 2 pixel block,
 // reads its eight texels once and writes the luma dwords and its share of the chroma planes.  Same values bit for bit: channels are
 // byte / 255 (unorm_of_byte), a chroma sample of a subsampled axis sits exactly between two texels (sub-texel fraction 128 / 256 for
@@ -542,7 +589,20 @@ static int conv_420_mode(const smr_ctx *ctx, const smr_frame *in) {
 }
 static bool conv_420_ok(const smr_ctx *ctx, const smr_frame *in) { return conv_420_mode(ctx, in) != 0; }
 
-bool smr_conv_rgb12_ok(const smr_ctx *ctx, const smr_frame *in) { return in && conv_420_ok(ctx, in) && 3u * in->width <= 7682u * 2u; }
+// k_yuv420_hi_to_rgba's frames (smr_convert_hi.h): P010 / planar 10-bit, width a multiple of 4 from 8, even height.  A luma row of a block is
+// one 8-byte load at 8 g: the Y plane's pointer and pitch are 8-byte aligned; the chroma loads are dwords: dword-aligned.  Nothing else: the
+// kernel requests no byte outside a row's own bytes, so owned and wrapped planes, wide and tight rows are one case.
+static bool conv_hi_mode(const smr_ctx *ctx, const smr_frame *in) {
+    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth(in->format)) return false;
+    const bool nv = in->format == SMR_FRAME_P010;
+    if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return false;
+    auto aligned = [](const smr_surface *s, uintptr_t a) { return s && (s->pitch & (a - 1)) == 0 && (((uintptr_t)s->ptr) & (a - 1)) == 0; };
+    if (!aligned(in->planes[0], 8) || !aligned(in->planes[1], 4) || (!nv && !aligned(in->planes[2], 4))) return false;
+    const u32 crow = nv ? 2u * in->width : in->width;  // bytes of a chroma row: w / 2 columns of 4 (2) bytes
+    return in->planes[0]->pitch >= 2u * in->width && in->planes[1]->pitch >= crow && (nv || in->planes[2]->pitch >= crow);
+}
+
+bool smr_conv_rgb12_ok(const smr_ctx *ctx, const smr_frame *in) { return in && (conv_420_ok(ctx, in) || conv_hi_mode(ctx, in)) && 3u * in->width <= 7682u * 2u; }
 
 // smr_frame_to_rgba for several frames: one launch for every 16 frames of a kind (k_yuv420_to_rgba planar / NV12, k_yuv_to_rgba_batch), the
 // others one by one.  Everything queued is launched before the call returns, errors included.
@@ -553,7 +613,7 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         if (!in[i] || !nodes[i]) return SMR_ERR_INVALID;
         if (rgb12 && rgb12[i]) {
             if (nodes[i]->fmt != SMR_PX_R8 || nodes[i]->w != 3 * in[i]->width || nodes[i]->h != in[i]->height || (nodes[i]->pitch & 3u) || (((uintptr_t)nodes[i]->ptr) & 3) ||
-                !conv_420_ok(ctx, in[i]))
+                !(conv_420_ok(ctx, in[i]) || conv_hi_mode(ctx, in[i])))
                 return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: an RGB12 node must be R8 %ux%u of a 4:2:0 frame the block converter takes", 3 * in[i]->width, in[i]->height);
         } else if (nodes[i]->fmt != SMR_PX_RGBA8 || nodes[i]->w != in[i]->width || nodes[i]->h != in[i]->height)
             return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: node surface must be RGBA8 %ux%u", in[i]->width, in[i]->height);
@@ -564,7 +624,8 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         u32 nb = 0;
         int mw = 0, mh = 0;
     };
-    Queue q[5];  // 0: k_yuv_to_rgba_batch | 1: k_yuv420_to_rgba planar | 2: ... NV12 | 3, 4: k_yuv420_to_rgba_tight planar, NV12
+    constexpr int NQ = 7;
+    Queue q[NQ];  // 0: k_yuv_to_rgba_batch | 1: k_yuv420_to_rgba planar | 2: ... NV12 | 3, 4: k_yuv420_to_rgba_tight planar, NV12 | 5, 6: k_yuv420_hi_to_rgba planar 10-bit, P010
     auto flush = [&](int k) -> int {
         Queue &Q = q[k];
         if (!Q.nb) return SMR_OK;
@@ -583,7 +644,8 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
             // kernel runs beside the other lane's kernels; configs[2] (8 640 units: 1.4 per wave at six) gains 2 % at five, configs[3]
             // (64 800 units) loses 1 % (profiles/r06_sensitivity.txt section 9)
             const int want = ctx->convert_wg_per_cu > 0 ? ctx->convert_wg_per_cu : (total >= 32768u ? 6 : 5);
-            const u32 per_cu = (u32)(want > 6 ? 6 : want);
+            // (the 10-bit kernels hold 101 registers: four workgroups per CU are resident, a fifth would only queue behind them)
+            const u32 per_cu = k >= 5 ? 4u : (u32)(want > 6 ? 6 : want);
             u32 blocks = (u32)ctx->cu_count * per_cu;
             if (blocks > (total + 3u) / 4u) blocks = (total + 3u) / 4u;
             // the partition (smr_convert_420.h): bands of block rows dealt to the XCDs, equal shares per wave inside an XCD
@@ -593,6 +655,8 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
             if (k == 1) hipLaunchKernelGGL(k_yuv420_to_rgba<false>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
             else if (k == 2) hipLaunchKernelGGL(k_yuv420_to_rgba<true>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
             else if (k == 3) hipLaunchKernelGGL(k_yuv420_to_rgba_tight<false>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
+            else if (k == 5) hipLaunchKernelGGL(k_yuv420_hi_to_rgba<false>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
+            else if (k == 6) hipLaunchKernelGGL(k_yuv420_hi_to_rgba<true>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
             else hipLaunchKernelGGL(k_yuv420_to_rgba_tight<true>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
         }
         Q.nb = 0; Q.mw = 0; Q.mh = 0;
@@ -601,16 +665,16 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
     };
     auto flush_all = [&]() -> int {
         int rc = SMR_OK;
-        for (int k = 0; k < 5; k++)
+        for (int k = 0; k < NQ; k++)
             if (int r = flush(k)) rc = rc ? rc : r;
         return rc;
     };
     for (u32 i = 0; i < n; i++) {
         const bool c12 = rgb12 && rgb12[i];
         const bool aligned16 = c12 || ((((uintptr_t)nodes[i]->ptr) & 15) == 0 && (nodes[i]->pitch & 15u) == 0);  // (the block kernels store 16 B)
-        const bool nv = in[i]->format == SMR_FRAME_NV12;
+        const bool nv = in[i]->format == SMR_FRAME_NV12 || in[i]->format == SMR_FRAME_P010;
         const int mode = conv_420_mode(ctx, in[i]);
-        const int k = !aligned16 ? -1 : mode ? (nv ? 2 : 1) + (mode == 2 ? 2 : 0) : conv_batchable(ctx, in[i]) ? 0 : -1;
+        const int k = !aligned16 ? -1 : conv_hi_mode(ctx, in[i]) ? (nv ? 6 : 5) : mode ? (nv ? 2 : 1) + (mode == 2 ? 2 : 0) : conv_batchable(ctx, in[i]) ? 0 : -1;
         if (k < 0) {
             if (int rc = smr_frame_to_rgba_general(ctx, in[i], nodes[i])) {
                 (void)flush_all();
@@ -631,7 +695,7 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         J.full = in[i]->format == SMR_FRAME_PLANAR_YUVJ420 ? 1 : 0;
         J.nv = nv ? 1 : 0;
         J.sx = in[i]->format != SMR_FRAME_PLANAR_YUV444 ? 1 : 0;
-        J.sy = (in[i]->format == SMR_FRAME_PLANAR_YUV420 || in[i]->format == SMR_FRAME_PLANAR_YUVJ420 || nv) ? 1 : 0;
+        J.sy = (in[i]->format == SMR_FRAME_PLANAR_YUV420 || in[i]->format == SMR_FRAME_PLANAR_YUVJ420 || in[i]->format == SMR_FRAME_PLANAR_YUV420P10 || nv) ? 1 : 0;
         Q.mw = (int)in[i]->width > Q.mw ? (int)in[i]->width : Q.mw;
         Q.mh = (int)in[i]->height > Q.mh ? (int)in[i]->height : Q.mh;
         if (Q.nb == MAX_CONV_JOBS)
@@ -674,6 +738,18 @@ static int smr_frame_to_rgba_general(smr_ctx *ctx, const smr_frame *in, smr_surf
         if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
         SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
         hipLaunchKernelGGL(k_yuv_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst, 0);
+        break;
+    }
+    case SMR_FRAME_PLANAR_YUV420P10: {
+        if (!in->planes[1] || !in->planes[2]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing chroma plane");
+        hipLaunchKernelGGL(k_yuv_hi_to_rgba<0>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), view_of(in->planes[1]),
+                           view_of(in->planes[2]), dst);
+        break;
+    }
+    case SMR_FRAME_P010: {
+        if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
+        SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
+        hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst);
         break;
     }
     case SMR_FRAME_UYVY422:
@@ -721,6 +797,7 @@ int smr_rgba_to_frame(smr_ctx *ctx, const smr_surface *node, const smr_frame *ou
     if (node->fmt != SMR_PX_RGBA8 || node->w != out->width || node->h != out->height)
         return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: node must be RGBA8 %ux%u", out->width, out->height);
     if (int rc = smr_validate_frame(ctx, out, "smr_rgba_to_frame")) return rc;
+    if (frame_format_is_hi_depth(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: frame format %u (10-bit) is input only", out->format);
     StageScope scope(ctx, SMR_STAGE_OUTPUT);
     const int w = (int)out->width, h = (int)out->height;
     SurfView src = view_of(node);
@@ -774,6 +851,7 @@ int smr_frame_fill_black(smr_ctx *ctx, const smr_frame *out) {
     if (ctx && out)
         if (int rc = smr_validate_frame(ctx, out, "smr_frame_fill_black")) return rc;
     if (!ctx || !out || !out->planes[0]) return SMR_ERR_INVALID;
+    if (frame_format_is_hi_depth(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_fill_black: frame format %u (10-bit) is input only", out->format);
     // RGBColor::BLACK.to_yuv(), smelter-render/src/scene/types.rs:28-41
     const float y = (0.0f * 0.85882354f) + (16.0f / 255.0f);
     const float c = ((0.0f + 0.5f) * 0.8784314f) + (16.0f / 255.0f);

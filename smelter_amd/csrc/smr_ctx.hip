@@ -473,6 +473,10 @@ static int plane_geometry(u32 format, u32 w, u32 h, u32 pw[3], u32 ph[3], u32 pf
         pw[0] = w; ph[0] = h; pw[1] = pw[2] = w; ph[1] = ph[2] = h; return 3;
     case SMR_FRAME_NV12:
         pw[0] = w; ph[0] = h; pw[1] = w / 2; ph[1] = h / 2; pf[1] = SMR_PX_RG8; return 2;
+    case SMR_FRAME_P010:  // NV12's geometry in 16-bit words
+        pw[0] = w; ph[0] = h; pf[0] = SMR_PX_R16; pw[1] = w / 2; ph[1] = h / 2; pf[1] = SMR_PX_RG16; return 2;
+    case SMR_FRAME_PLANAR_YUV420P10:  // 4:2:0's
+        pw[0] = w; ph[0] = h; pw[1] = pw[2] = w / 2; ph[1] = ph[2] = h / 2; pf[0] = pf[1] = pf[2] = SMR_PX_R16; return 3;
     case SMR_FRAME_UYVY422:
     case SMR_FRAME_YUYV422:
         pw[0] = w / 2; ph[0] = h; pf[0] = SMR_PX_RGBA8; return 1;

@@ -43,7 +43,7 @@ bool fused_disabled(smr_ctx *ctx) {  // SMR_OPT_FUSED_KERNELS
 }
 
 // every YUV-family FrameData variant converts to alpha == 1 (wgpu/format/*_to_rgba.wgsl return vec4(.., 1.0))
-bool frame_is_opaque(u32 fmt) { return fmt <= SMR_FRAME_NV12; }
+bool frame_is_opaque(u32 fmt) { return frame_format_is_opaque_ycbcr(fmt); }
 
 // surface-cache slots: smr_internal.h (one table, disjoint ranges)
 constexpr size_t SLOT_TARGET = SMR_SLOT_TARGET, SLOT_INGEST_NODE = SMR_SLOT_INGEST_NODE, SLOT_NODE0 = SMR_SLOT_NODE0, SLOT_TILE0 = SMR_SLOT_TILE0,
@@ -702,7 +702,7 @@ static int ingest_resample_one(smr_ctx *ctx, const smr_frame *in, const float cr
         rc = launch_wave(ctx, wjobs, nullptr, true, false, false, false, true);
         return rc == SMR_OK ? kind : rc;
     }
-    if (!fused_disabled(ctx) && in->format <= SMR_FRAME_NV12 && ctx->ingest_impl != SMR_INGEST_VALU_F32) {
+    if (!fused_disabled(ctx) && frame_format_is_opaque_ycbcr(in->format) && ctx->ingest_impl != SMR_INGEST_VALU_F32) {
         smr_surface *node = smr_cached_surface(ctx, SLOT_INGEST_NODE, in->width, in->height, SMR_PX_RGBA8);
         if (!node) return SMR_ERR_OOM;
         bool single = false;
@@ -802,7 +802,7 @@ extern "C" int smr_ingest_resample_batch(smr_ctx *ctx, const smr_frame *const *i
             wjobs_rgb12.push_back(J);
             continue;
         }
-        if (fused && !fused_conversion(ctx) && ctx->ingest_impl != SMR_INGEST_VALU_F32 && in[i]->format <= SMR_FRAME_NV12) {
+        if (fused && !fused_conversion(ctx) && ctx->ingest_impl != SMR_INGEST_VALU_F32 && frame_format_is_opaque_ycbcr(in[i]->format)) {
             SurfView probe;  // (the geometry test needs the node's size, not its pixels)
             probe.ptr = nullptr; probe.pitch = (in[i]->width * 4u + 255u) & ~255u; probe.w = (int)in[i]->width; probe.h = (int)in[i]->height;
             bool single = false;

@@ -1442,6 +1442,7 @@ int make_wave_job(smr_ctx *ctx, const smr_frame *f, const smr_resample_plan &pla
 // windows (vertical bands on the origin-0 chunk grid: axis 5), 16-byte aligned tile rows.  *cls: 0 <4, 2> | 1 <8, 3> | 2 <8, 2>.
 bool can_fuse_planes(smr_ctx *ctx, const smr_frame *f, const smr_resample_plan &plan, const smr_surface *tile, int *cls = nullptr) {
     if (!ctx->plane_source || ctx->ingest_impl == SMR_INGEST_VALU_F32 || !f || !smr_conv_rgb12_ok(ctx, f)) return false;
+    if (f->format != SMR_FRAME_PLANAR_YUV420 && f->format != SMR_FRAME_PLANAR_YUVJ420 && f->format != SMR_FRAME_NV12) return false;  // (8-bit planes only: the in-wave conversion reads bytes)
     if (!(plan.kind == 2 && plan.levels[0] == 0 && plan.levels[1] == 0 && plan.axis[0] == 0 && plan.axis[1] == 1)) return false;
     if (((uintptr_t)tile->ptr % 16) || (tile->pitch % 16) || f->height < 4) return false;
     int NKS, KV, unused;

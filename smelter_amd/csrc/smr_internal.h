@@ -294,9 +294,15 @@ static inline u32 bytes_per_px(u32 fmt) {
     case SMR_PX_RGBA16F: return 8;
     case SMR_PX_R8: return 1;
     case SMR_PX_RG8: return 2;
+    case SMR_PX_R16: return 2;
+    case SMR_PX_RG16: return 4;
     default: return 0;
     }
 }
+
+// frame_format_is_opaque_ycbcr ("this frame format is opaque Y'CbCr"), frame_format_is_hi_depth: in a header without HIP, because the
+// renderer's host code (host/renderer.cpp: plain C++, built without HIP by tests/san too) asks the same questions
+#include "smr_frame_formats.h"
 
 // ------------------------------------------------------------------ device helpers
 #ifdef __HIPCC__

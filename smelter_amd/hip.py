@@ -11,9 +11,9 @@ from typing import Tuple, List, Optional, Sequence
 import numpy as np
 
 from . import _ffi
-from ._ffi import (FRAME_ARGB, FRAME_BGRA, FRAME_NV12, FRAME_PLANAR_YUV420, FRAME_PLANAR_YUV422, FRAME_PLANAR_YUV444,
-                   FRAME_PLANAR_YUVJ420, FRAME_RGBA, FRAME_UYVY422, FRAME_YUYV422, MODE_CPU_OPTIMIZED, MODE_GPU_OPTIMIZED,
-                   PX_R8, PX_RG8, PX_RGBA8, PX_RGBA16F)
+from ._ffi import (FRAME_ARGB, FRAME_BGRA, FRAME_NV12, FRAME_P010, FRAME_PLANAR_YUV420, FRAME_PLANAR_YUV420P10, FRAME_PLANAR_YUV422,
+                   FRAME_PLANAR_YUV444, FRAME_PLANAR_YUVJ420, FRAME_RGBA, FRAME_UYVY422, FRAME_YUYV422, MODE_CPU_OPTIMIZED,
+                   MODE_GPU_OPTIMIZED, PX_R8, PX_R16, PX_RG8, PX_RG16, PX_RGBA8, PX_RGBA16F)
 from ._ffi import (SHADER_CIRCLE_LAYOUT, SHADER_COLOR_BY_TEXTURE_COUNT, SHADER_FADE_TO_BALL, SHADER_GAUSSIAN_BLUR,  # noqa: F401
                    SHADER_GRADIENT, SHADER_LAYOUT_PLANES, SHADER_MAX_SOURCES, SHADER_RED_BORDER, SHADER_SILLY)
 
@@ -45,6 +45,10 @@ class Surface:
             return (self.h, self.w, 4), np.uint16
         if self.fmt == PX_RG8:
             return (self.h, self.w, 2), np.uint8
+        if self.fmt == PX_R16:
+            return (self.h, self.w), np.uint16
+        if self.fmt == PX_RG16:
+            return (self.h, self.w, 2), np.uint16
         return (self.h, self.w), np.uint8
 
     def upload(self, arr) -> "Surface":
@@ -80,33 +84,39 @@ class DeviceFrame:
 
     def plane_shapes(self):
         w, h, f = self.w, self.h, self.fmt
-        if f in (FRAME_PLANAR_YUV420, FRAME_PLANAR_YUVJ420):
+        if f in (FRAME_PLANAR_YUV420, FRAME_PLANAR_YUVJ420, FRAME_PLANAR_YUV420P10):
             return [(h, w), (h // 2, w // 2), (h // 2, w // 2)]
         if f == FRAME_PLANAR_YUV422:
             return [(h, w), (h, w // 2), (h, w // 2)]
         if f == FRAME_PLANAR_YUV444:
             return [(h, w), (h, w), (h, w)]
-        if f == FRAME_NV12:
+        if f in (FRAME_NV12, FRAME_P010):
             return [(h, w), (h // 2, w // 2, 2)]
         if f in (FRAME_UYVY422, FRAME_YUYV422):
             return [(h, w // 2, 4)]
         return [(h, w, 4)]
 
+    def plane_dtype(self):
+        """The element type of every plane: 16-bit words for the 10-bit formats, bytes otherwise."""
+        return np.uint16 if self.fmt in (FRAME_P010, FRAME_PLANAR_YUV420P10) else np.uint8
+
     def upload(self, planes: Sequence[np.ndarray]) -> "DeviceFrame":
         shapes = self.plane_shapes()
-        keep = [np.ascontiguousarray(p, dtype=np.uint8).reshape(s) for p, s in zip(planes, shapes)]
+        keep = [np.ascontiguousarray(p, dtype=self.plane_dtype()).reshape(s) for p, s in zip(planes, shapes)]
         ptrs = (C.c_void_p * 3)(*[k.ctypes.data for k in keep] + [None] * (3 - len(keep)))
         self.ctx._check(self.ctx.lib.smr_frame_upload(self.ctx.handle, C.byref(self.c), ptrs))
         return self
 
     def download(self) -> List[np.ndarray]:
-        outs = [np.empty(s, np.uint8) for s in self.plane_shapes()]
+        outs = [np.empty(s, self.plane_dtype()) for s in self.plane_shapes()]
         ptrs = (C.c_void_p * 3)(*[o.ctypes.data for o in outs] + [None] * (3 - len(outs)))
         self.ctx._check(self.ctx.lib.smr_frame_download(self.ctx.handle, C.byref(self.c), ptrs))
         return outs
 
     def pinned_planes(self) -> List[np.ndarray]:
         """Host plane buffers in pinned memory (smr_host_alloc), shaped like this frame's planes; freed with the context."""
+        if self.plane_dtype() == np.uint16:  # (host_array hands out bytes: twice as many per row, seen as words)
+            return [self.ctx.host_array(tuple(s[:-1]) + (2 * s[-1],)).view(np.uint16) for s in self.plane_shapes()]
         return [self.ctx.host_array(s) for s in self.plane_shapes()]
 
     def upload_async(self, pinned: Sequence[np.ndarray]):
@@ -346,7 +356,10 @@ class Context:
         assert len(shapes) == len(planes), "one (pointer, pitch) pair per plane"
         f.surfaces = []
         for i, ((dptr, pitch), shape) in enumerate(zip(planes, shapes)):
-            pf = PX_RGBA8 if len(shape) == 3 and shape[2] == 4 else PX_RG8 if len(shape) == 3 else PX_R8
+            if f.plane_dtype() == np.uint16:
+                pf = PX_RG16 if len(shape) == 3 else PX_R16
+            else:
+                pf = PX_RGBA8 if len(shape) == 3 and shape[2] == 4 else PX_RG8 if len(shape) == 3 else PX_R8
             s = self.wrap(dptr, pitch, shape[1], shape[0], pf)
             f.surfaces.append(s)  # (kept alive with the frame)
             f.c.planes[i] = s.handle.value if hasattr(s.handle, "value") else s.handle
