@@ -76,15 +76,32 @@ typedef enum smr_frame_format {
      * A 10-bit code c is the 8-bit code c / 4 with two more fractional bits: its unorm value is (c * 0.25) / 255, and from there on the
      * conversion is planar_yuv_to_rgba.wgsl / nv12_to_rgba.wgsl unchanged (limited range 64 .. 940 is exactly 16 .. 235) — a frame whose
      * codes are 4 b has, byte for byte, the node texture of the 8-bit frame with bytes b.
-     * Not offered: full-range 10-bit, 4:2:2 / 4:4:4 10-bit (P210, Y210), 12-bit, 10-bit outputs, and these formats on the plane-source
+     * Not offered: full-range 10-bit, 4:4:4 10-bit, Y210, 12-bit, 10-bit outputs, and these formats on the plane-source
      * route (SMR_OPT_PLANE_SOURCE) or the laboratory fused conversion — both keep rejecting the formats they do not name. */
     SMR_FRAME_P010 = 10,              /* {Y: R16 w x h, UV: RG16 w/2 x h/2}; code = word >> 6, the low six bits are ignored */
     SMR_FRAME_PLANAR_YUV420P10 = 11,  /* {Y, U, V}, all R16; code = word & 0x3ff, the high six bits are ignored */
+    /* 10-bit 4:2:2, what SDI capture cards (v210) and ProRes 422 / DNxHR / XAVC / H.264 Hi422 decoders (yuv422p10le, P210) hand over.
+     * Limited range, opaque, INPUT ONLY like the two above, and the same value rule: a code c has the unorm value (f32(c) * 0.25f) / 255.0f.
+     * Planar 10-bit and P210 continue with planar_yuv_to_rgba.wgsl as it samples a 4:2:2 frame: chroma bilinear horizontally (weights
+     * .75 / .25, clamp to edge), the texel itself vertically — codes 4 b give, byte for byte, the node texture of the 8-bit
+     * SMR_FRAME_PLANAR_YUV422 frame with bytes b.
+     * v210 continues with interleaved_uyvy_to_rgba.wgsl: pixel x takes luma Y[x] and the chroma of pair x / 2, no interpolation, then the
+     * limited-range conversion — defined that way for every width, odd ones included; for even widths from 8 up codes 4 b give, byte for
+     * byte, the node texture of the UYVY frame with bytes b.
+     * v210 layout: a dword holds three codes, lo in bits 0-9, mid in bits 10-19, hi in bits 20-29; bits 30-31 are ignored.  Six pixels are
+     * four dwords, Cb(j) / Cr(j) belonging to the group's pixel pair j:
+     *      d0 = Cb(0) Y0 Cr(0) | d1 = Y1 Cb(1) Y2 | d2 = Cr(1) Y3 Cb(2) | d3 = Y4 Cr(2) Y5          (lo mid hi)
+     * The last group may be partly filled: components of pixels at or beyond the width are ignored, but the group's 16 bytes are part of
+     * the row (nothing past the row is read).  A capture card's row stride, ((w + 47) / 48) * 128 bytes, is the pitch of a wrapped plane. */
+    SMR_FRAME_PLANAR_YUV422P10 = 12,  /* {Y: R16 w x h, U, V: R16 w/2 x h}: SMR_FRAME_PLANAR_YUV422's geometry; code = word & 0x3ff */
+    SMR_FRAME_P210 = 13,              /* {Y: R16 w x h, UV: RG16 w/2 x h}; code = word >> 6 */
+    SMR_FRAME_V210 = 14,              /* one SMR_PX_RGBA8 plane of 4 * ceil(w / 6) texels x h: a texel is one little-endian dword */
 } smr_frame_format;
 
 /* One video frame resident in HBM: up to three pitched plane surfaces.
- * planes[] per format: planar YUV {Y,U,V}; NV12 {Y (R8), UV (RG8)}; P010 {Y (R16), UV (RG16)}; planar 10-bit {Y,U,V} (R16); packed formats {data}.
- * UYVY/YUYV planes are RGBA8 surfaces of width/2 texels (wgpu/texture/interleaved_yuv422.rs). */
+ * planes[] per format: planar YUV {Y,U,V}; NV12 {Y (R8), UV (RG8)}; P010 / P210 {Y (R16), UV (RG16)}; planar 10-bit {Y,U,V} (R16); packed formats {data}.
+ * UYVY/YUYV planes are RGBA8 surfaces of width/2 texels (wgpu/texture/interleaved_yuv422.rs); a v210 plane is an RGBA8 surface of
+ * 4 * ceil(width / 6) texels. */
 typedef struct smr_frame {
     uint32_t format; /* smr_frame_format */
     uint32_t width;
@@ -911,7 +928,8 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      the Text raster cache (smr_renderer_text_stats: no struct changed, no kernel counter slot was added, no existing scene renders
  *      differently);
  *      10-bit 4:2:0 input frames (SMR_PX_R16, SMR_PX_RG16, SMR_FRAME_P010, SMR_FRAME_PLANAR_YUV420P10: input only, no struct changed, no
- *      kernel counter slot was added, no 8-bit frame converts differently).
+ *      kernel counter slot was added, no 8-bit frame converts differently);
+ *      10-bit 4:2:2 input frames (SMR_FRAME_PLANAR_YUV422P10, SMR_FRAME_P210, SMR_FRAME_V210: likewise).
  * The two removed names are kept as macros that do not compile, so that a source written against version 1 fails where it uses them
  * instead of silently meaning something else. */
 #define SMR_ABI_VERSION 2

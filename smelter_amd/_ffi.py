@@ -18,6 +18,7 @@ PX_R16, PX_RG16 = 4, 5  # 16-bit words: the planes of the 10-bit frame formats
 (FRAME_PLANAR_YUV420, FRAME_PLANAR_YUV422, FRAME_PLANAR_YUV444, FRAME_PLANAR_YUVJ420, FRAME_UYVY422, FRAME_YUYV422,
  FRAME_NV12, FRAME_BGRA, FRAME_ARGB, FRAME_RGBA) = range(10)
 FRAME_P010, FRAME_PLANAR_YUV420P10 = 10, 11  # 10-bit 4:2:0, limited range, input only (code = word >> 6 | word & 0x3ff)
+FRAME_PLANAR_YUV422P10, FRAME_P210, FRAME_V210 = 12, 13, 14  # 10-bit 4:2:2, limited range, input only (word & 0x3ff | word >> 6 | three codes per dword)
 MAX_MASKS = 20
 NO_SOURCE = 0xFFFFFFFF
 SOURCE_NONE, SOURCE_SURFACE, SOURCE_FRAME, SOURCE_OPAQUE_SURFACE = 0, 1, 2, 3

@@ -12,6 +12,7 @@
 #include "smr_convert_dev.h"
 #include "smr_convert_420.h"
 #include "smr_convert_hi.h"
+#include "smr_convert_hi422.h"
 #include "smr_svg_nodes.h"
 
 namespace {
@@ -85,6 +86,20 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_hi_to_rgba(SurfView yp, SurfView 
     } else {
         for (int i = 0; i < 4 && x0 + i < dst.w; i++) *(u32 *)(row + (size_t)(x0 + i) * 4) = px[i];
     }
+}
+
+// 10-bit 4:2:2, any geometry.  Planar 10-bit and P210 frames take k_yuv_hi_to_rgba above: its sampler asks the planes for their size, and a
+// (w / 2) x h chroma plane is all that differs.  This is v210 (smr_convert_hi422.h): k_interleaved422_to_rgba's shape, one pixel per thread,
+// luma Y[x] and the chroma of pair x / 2 for every width (include/smr.h), then the limited-range conversion.
+template <int LAYOUT>
+__global__ __launch_bounds__(BLOCK) void k_yuv422_hi_to_rgba_any(SurfView src, SurfView dst) {
+    static_assert(LAYOUT == CV422_V210, "planar 10-bit and P210 are served by k_yuv_hi_to_rgba");
+    const int x = blockIdx.x * BLOCK + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= dst.w) return;
+    u32 yc, cb, cr;
+    cv210_pixel_codes(src.ptr + (size_t)y * src.pitch, x, yc, cb, cr);
+    *(u32 *)(dst.ptr + (size_t)y * dst.pitch + (size_t)x * 4) = yuv_to_rgb_px(cvhi_unorm_of_code(yc), cvhi_unorm_of_code(cb), cvhi_unorm_of_code(cr), false);
 }
 
 // The same pass for planar 4:2:0 (limited or full range), 4:2:2, 4:4:4 and NV12 frames, several frames per launch: what k_yuv_to_rgba
@@ -453,6 +468,16 @@ __global__ __launch_bounds__(BLOCK) void k_yuv420_hi_to_rgba(const ConvBatch B) 
     cvhi_share<P010>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, threadIdx.x & 63u, s_ylut, s_ulut);
 }
 
+// 10-bit 4:2:2 frames the block converter takes (smr_convert_hi422.h, conv_hi422_mode): the launch above with the 4:2:2 fetch — planar 10-bit,
+// P210 (a chroma row per luma row) or v210 (16 bytes of the row per thread, the fields chosen by g % 3).  The same two tables.
+template <int LAYOUT>
+__global__ __launch_bounds__(BLOCK) void k_yuv422_hi_to_rgba(const ConvBatch B) {
+    __shared__ float s_ylut[CVHI_CODES], s_ulut[CVHI_CODES];
+    cvhi_build_tables(s_ylut, s_ulut, threadIdx.x, BLOCK);
+    __syncthreads();
+    cv422_share<LAYOUT>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, threadIdx.x & 63u, s_ylut, s_ulut);
+}
+
 // rgba_to_yuv.wgsl's three passes (k_rgba_to_y + k_rgba_to_chroma) in one launch for even-sized frames: a thread owns a 4 x 2 pixel block,
 // reads its eight texels once and writes the luma dwords and its share of the chroma planes.  Same values bit for bit: channels are
 // byte / 255 (unorm_of_byte), a chroma sample of a subsampled axis sits exactly between two texels (sub-texel fraction 128 / 256 for
@@ -593,7 +618,7 @@ static bool conv_420_ok(const smr_ctx *ctx, const smr_frame *in) { return conv_4
 // one 8-byte load at 8 g: the Y plane's pointer and pitch are 8-byte aligned; the chroma loads are dwords: dword-aligned.  Nothing else: the
 // kernel requests no byte outside a row's own bytes, so owned and wrapped planes, wide and tight rows are one case.
 static bool conv_hi_mode(const smr_ctx *ctx, const smr_frame *in) {
-    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth(in->format)) return false;
+    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth(in->format) || frame_format_is_hi_depth_422(in->format)) return false;
     const bool nv = in->format == SMR_FRAME_P010;
     if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return false;
     auto aligned = [](const smr_surface *s, uintptr_t a) { return s && (s->pitch & (a - 1)) == 0 && (((uintptr_t)s->ptr) & (a - 1)) == 0; };
@@ -602,7 +627,25 @@ static bool conv_hi_mode(const smr_ctx *ctx, const smr_frame *in) {
     return in->planes[0]->pitch >= 2u * in->width && in->planes[1]->pitch >= crow && (nv || in->planes[2]->pitch >= crow);
 }
 
-bool smr_conv_rgb12_ok(const smr_ctx *ctx, const smr_frame *in) { return in && (conv_420_ok(ctx, in) || conv_hi_mode(ctx, in)) && 3u * in->width <= 7682u * 2u; }
+// k_yuv422_hi_to_rgba's frames (smr_convert_hi422.h): planar 10-bit 4:2:2, P210, v210; width a multiple of 4 from 8, even height.  A luma row
+// of a block is one 8-byte load at 8 g, a v210 row of a block two 8-byte loads at 32 (g / 3) + 8 (g % 3): the Y plane's (v210: the plane's)
+// pointer and pitch are 8-byte aligned; the chroma loads are dwords: dword-aligned.  Nothing else: the kernel requests no byte outside a row's
+// own bytes, so owned and wrapped planes, wide and tight rows (a capture card's stride among them) are one case.
+static bool conv_hi422_mode(const smr_ctx *ctx, const smr_frame *in) {
+    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth_422(in->format)) return false;
+    if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return false;
+    auto aligned = [](const smr_surface *s, uintptr_t a) { return s && (s->pitch & (a - 1)) == 0 && (((uintptr_t)s->ptr) & (a - 1)) == 0; };
+    if (!aligned(in->planes[0], 8)) return false;
+    if (in->format == SMR_FRAME_V210) return in->planes[0]->pitch >= 16u * ((in->width + 5u) / 6u);
+    const bool nv = in->format == SMR_FRAME_P210;
+    if (!aligned(in->planes[1], 4) || (!nv && !aligned(in->planes[2], 4))) return false;
+    const u32 crow = nv ? 2u * in->width : in->width;  // bytes of a chroma row: w / 2 columns of 4 (2) bytes
+    return in->planes[0]->pitch >= 2u * in->width && in->planes[1]->pitch >= crow && (nv || in->planes[2]->pitch >= crow);
+}
+
+bool smr_conv_rgb12_ok(const smr_ctx *ctx, const smr_frame *in) {
+    return in && (conv_420_ok(ctx, in) || conv_hi_mode(ctx, in) || conv_hi422_mode(ctx, in)) && 3u * in->width <= 7682u * 2u;
+}
 
 // smr_frame_to_rgba for several frames: one launch for every 16 frames of a kind (k_yuv420_to_rgba planar / NV12, k_yuv_to_rgba_batch), the
 // others one by one.  Everything queued is launched before the call returns, errors included.
@@ -613,7 +656,7 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         if (!in[i] || !nodes[i]) return SMR_ERR_INVALID;
         if (rgb12 && rgb12[i]) {
             if (nodes[i]->fmt != SMR_PX_R8 || nodes[i]->w != 3 * in[i]->width || nodes[i]->h != in[i]->height || (nodes[i]->pitch & 3u) || (((uintptr_t)nodes[i]->ptr) & 3) ||
-                !(conv_420_ok(ctx, in[i]) || conv_hi_mode(ctx, in[i])))
+                !(conv_420_ok(ctx, in[i]) || conv_hi_mode(ctx, in[i]) || conv_hi422_mode(ctx, in[i])))
                 return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: an RGB12 node must be R8 %ux%u of a 4:2:0 frame the block converter takes", 3 * in[i]->width, in[i]->height);
         } else if (nodes[i]->fmt != SMR_PX_RGBA8 || nodes[i]->w != in[i]->width || nodes[i]->h != in[i]->height)
             return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: node surface must be RGBA8 %ux%u", in[i]->width, in[i]->height);
@@ -624,8 +667,10 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         u32 nb = 0;
         int mw = 0, mh = 0;
     };
-    constexpr int NQ = 7;
-    Queue q[NQ];  // 0: k_yuv_to_rgba_batch | 1: k_yuv420_to_rgba planar | 2: ... NV12 | 3, 4: k_yuv420_to_rgba_tight planar, NV12 | 5, 6: k_yuv420_hi_to_rgba planar 10-bit, P010
+    constexpr int NQ = 10;
+    // 0: k_yuv_to_rgba_batch | 1: k_yuv420_to_rgba planar | 2: ... NV12 | 3, 4: k_yuv420_to_rgba_tight planar, NV12 | 5, 6: k_yuv420_hi_to_rgba planar
+    // 10-bit, P010 | 7, 8, 9: k_yuv422_hi_to_rgba planar 10-bit 4:2:2, P210, v210
+    Queue q[NQ];
     auto flush = [&](int k) -> int {
         Queue &Q = q[k];
         if (!Q.nb) return SMR_OK;
@@ -645,7 +690,19 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
             // (64 800 units) loses 1 % (profiles/r06_sensitivity.txt section 9)
             const int want = ctx->convert_wg_per_cu > 0 ? ctx->convert_wg_per_cu : (total >= 32768u ? 6 : 5);
             // (the 10-bit kernels hold 101 registers: four workgroups per CU are resident, a fifth would only queue behind them)
-            const u32 per_cu = k >= 5 ? 4u : (u32)(want > 6 ? 6 : want);
+            u32 per_cu = k >= 5 ? 4u : (u32)(want > 6 ? 6 : want);
+            if (k >= 7) {  // the 4:2:2 kernels: as many workgroups per CU as the kernel's own registers and LDS keep resident (asked once per context)
+                const void *kern = k == 7 ? (const void *)k_yuv422_hi_to_rgba<CV422_PLANAR> : k == 8 ? (const void *)k_yuv422_hi_to_rgba<CV422_P210> : (const void *)k_yuv422_hi_to_rgba<CV422_V210>;
+                int resident = 0;
+                for (auto &o : ctx->mfma_occupancy)
+                    if (o.kernel == 2000 + k && o.lds == 0) resident = o.per_cu;
+                if (!resident) {
+                    SMR_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, BLOCK, 0));
+                    if (resident < 1) resident = 1;
+                    ctx->mfma_occupancy.push_back({2000 + k, 0, resident});
+                }
+                per_cu = (u32)(resident > 6 ? 6 : resident);
+            }
             u32 blocks = (u32)ctx->cu_count * per_cu;
             if (blocks > (total + 3u) / 4u) blocks = (total + 3u) / 4u;
             // the partition (smr_convert_420.h): bands of block rows dealt to the XCDs, equal shares per wave inside an XCD
@@ -657,6 +714,9 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
             else if (k == 3) hipLaunchKernelGGL(k_yuv420_to_rgba_tight<false>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
             else if (k == 5) hipLaunchKernelGGL(k_yuv420_hi_to_rgba<false>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
             else if (k == 6) hipLaunchKernelGGL(k_yuv420_hi_to_rgba<true>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
+            else if (k == 7) hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_PLANAR>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
+            else if (k == 8) hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_P210>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
+            else if (k == 9) hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_V210>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
             else hipLaunchKernelGGL(k_yuv420_to_rgba_tight<true>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
         }
         Q.nb = 0; Q.mw = 0; Q.mh = 0;
@@ -672,9 +732,9 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
     for (u32 i = 0; i < n; i++) {
         const bool c12 = rgb12 && rgb12[i];
         const bool aligned16 = c12 || ((((uintptr_t)nodes[i]->ptr) & 15) == 0 && (nodes[i]->pitch & 15u) == 0);  // (the block kernels store 16 B)
-        const bool nv = in[i]->format == SMR_FRAME_NV12 || in[i]->format == SMR_FRAME_P010;
+        const bool nv = in[i]->format == SMR_FRAME_NV12 || in[i]->format == SMR_FRAME_P010 || in[i]->format == SMR_FRAME_P210;
         const int mode = conv_420_mode(ctx, in[i]);
-        const int k = !aligned16 ? -1 : conv_hi_mode(ctx, in[i]) ? (nv ? 6 : 5) : mode ? (nv ? 2 : 1) + (mode == 2 ? 2 : 0) : conv_batchable(ctx, in[i]) ? 0 : -1;
+        const int k = !aligned16 ? -1 : conv_hi422_mode(ctx, in[i]) ? (in[i]->format == SMR_FRAME_V210 ? 9 : nv ? 8 : 7) : conv_hi_mode(ctx, in[i]) ? (nv ? 6 : 5) : mode ? (nv ? 2 : 1) + (mode == 2 ? 2 : 0) : conv_batchable(ctx, in[i]) ? 0 : -1;
         if (k < 0) {
             if (int rc = smr_frame_to_rgba_general(ctx, in[i], nodes[i])) {
                 (void)flush_all();
@@ -684,7 +744,8 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         }
         Queue &Q = q[k];
         ConvJob &J = Q.B.j[Q.nb++];
-        const bool packed = in[i]->format == SMR_FRAME_UYVY422 || in[i]->format == SMR_FRAME_YUYV422 || in[i]->format == SMR_FRAME_BGRA || in[i]->format == SMR_FRAME_ARGB;
+        const bool packed = in[i]->format == SMR_FRAME_UYVY422 || in[i]->format == SMR_FRAME_YUYV422 || in[i]->format == SMR_FRAME_BGRA || in[i]->format == SMR_FRAME_ARGB ||
+                            in[i]->format == SMR_FRAME_V210;
         J.yp = view_of(in[i]->planes[0]);
         J.up = packed ? J.yp : view_of(in[i]->planes[1]);
         J.vp = packed || nv ? J.up : view_of(in[i]->planes[2]);
@@ -695,7 +756,7 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         J.full = in[i]->format == SMR_FRAME_PLANAR_YUVJ420 ? 1 : 0;
         J.nv = nv ? 1 : 0;
         J.sx = in[i]->format != SMR_FRAME_PLANAR_YUV444 ? 1 : 0;
-        J.sy = (in[i]->format == SMR_FRAME_PLANAR_YUV420 || in[i]->format == SMR_FRAME_PLANAR_YUVJ420 || in[i]->format == SMR_FRAME_PLANAR_YUV420P10 || nv) ? 1 : 0;
+        J.sy = (in[i]->format == SMR_FRAME_PLANAR_YUV420 || in[i]->format == SMR_FRAME_PLANAR_YUVJ420 || in[i]->format == SMR_FRAME_PLANAR_YUV420P10 || (nv && in[i]->format != SMR_FRAME_P210)) ? 1 : 0;
         Q.mw = (int)in[i]->width > Q.mw ? (int)in[i]->width : Q.mw;
         Q.mh = (int)in[i]->height > Q.mh ? (int)in[i]->height : Q.mh;
         if (Q.nb == MAX_CONV_JOBS)
@@ -752,6 +813,21 @@ static int smr_frame_to_rgba_general(smr_ctx *ctx, const smr_frame *in, smr_surf
         hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst);
         break;
     }
+    case SMR_FRAME_PLANAR_YUV422P10: {  // (k_yuv_hi_to_rgba samples the planes at their own size: (w / 2) x h here)
+        if (!in->planes[1] || !in->planes[2]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing chroma plane");
+        hipLaunchKernelGGL(k_yuv_hi_to_rgba<0>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), view_of(in->planes[1]),
+                           view_of(in->planes[2]), dst);
+        break;
+    }
+    case SMR_FRAME_P210: {
+        if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
+        SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
+        hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst);
+        break;
+    }
+    case SMR_FRAME_V210:
+        hipLaunchKernelGGL(k_yuv422_hi_to_rgba_any<CV422_V210>, grid_px(w, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), dst);
+        break;
     case SMR_FRAME_UYVY422:
     case SMR_FRAME_YUYV422:
         hipLaunchKernelGGL(k_interleaved422_to_rgba, grid_px(w, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), dst,

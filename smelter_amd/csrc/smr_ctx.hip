@@ -477,6 +477,12 @@ static int plane_geometry(u32 format, u32 w, u32 h, u32 pw[3], u32 ph[3], u32 pf
         pw[0] = w; ph[0] = h; pf[0] = SMR_PX_R16; pw[1] = w / 2; ph[1] = h / 2; pf[1] = SMR_PX_RG16; return 2;
     case SMR_FRAME_PLANAR_YUV420P10:  // 4:2:0's
         pw[0] = w; ph[0] = h; pw[1] = pw[2] = w / 2; ph[1] = ph[2] = h / 2; pf[0] = pf[1] = pf[2] = SMR_PX_R16; return 3;
+    case SMR_FRAME_PLANAR_YUV422P10:  // 4:2:2's in 16-bit words
+        pw[0] = w; ph[0] = h; pw[1] = pw[2] = w / 2; ph[1] = ph[2] = h; pf[0] = pf[1] = pf[2] = SMR_PX_R16; return 3;
+    case SMR_FRAME_P210:  // P010's with chroma rows equal to luma rows
+        pw[0] = w; ph[0] = h; pf[0] = SMR_PX_R16; pw[1] = w / 2; ph[1] = h; pf[1] = SMR_PX_RG16; return 2;
+    case SMR_FRAME_V210:  // one dword per texel, four per group of six pixels (the last group may be partly filled), as UYVY's plane is w / 2 texels
+        pw[0] = 4 * ((w + 5) / 6); ph[0] = h; pf[0] = SMR_PX_RGBA8; return 1;
     case SMR_FRAME_UYVY422:
     case SMR_FRAME_YUYV422:
         pw[0] = w / 2; ph[0] = h; pf[0] = SMR_PX_RGBA8; return 1;

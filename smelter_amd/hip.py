@@ -11,8 +11,8 @@ from typing import Tuple, List, Optional, Sequence
 import numpy as np
 
 from . import _ffi
-from ._ffi import (FRAME_ARGB, FRAME_BGRA, FRAME_NV12, FRAME_P010, FRAME_PLANAR_YUV420, FRAME_PLANAR_YUV420P10, FRAME_PLANAR_YUV422,
-                   FRAME_PLANAR_YUV444, FRAME_PLANAR_YUVJ420, FRAME_RGBA, FRAME_UYVY422, FRAME_YUYV422, MODE_CPU_OPTIMIZED,
+from ._ffi import (FRAME_ARGB, FRAME_BGRA, FRAME_NV12, FRAME_P010, FRAME_P210, FRAME_PLANAR_YUV420, FRAME_PLANAR_YUV420P10, FRAME_PLANAR_YUV422,
+                   FRAME_PLANAR_YUV422P10, FRAME_V210, FRAME_PLANAR_YUV444, FRAME_PLANAR_YUVJ420, FRAME_RGBA, FRAME_UYVY422, FRAME_YUYV422, MODE_CPU_OPTIMIZED,
                    MODE_GPU_OPTIMIZED, PX_R8, PX_R16, PX_RG8, PX_RG16, PX_RGBA8, PX_RGBA16F)
 from ._ffi import (SHADER_CIRCLE_LAYOUT, SHADER_COLOR_BY_TEXTURE_COUNT, SHADER_FADE_TO_BALL, SHADER_GAUSSIAN_BLUR,  # noqa: F401
                    SHADER_GRADIENT, SHADER_LAYOUT_PLANES, SHADER_MAX_SOURCES, SHADER_RED_BORDER, SHADER_SILLY)
@@ -86,8 +86,12 @@ class DeviceFrame:
         w, h, f = self.w, self.h, self.fmt
         if f in (FRAME_PLANAR_YUV420, FRAME_PLANAR_YUVJ420, FRAME_PLANAR_YUV420P10):
             return [(h, w), (h // 2, w // 2), (h // 2, w // 2)]
-        if f == FRAME_PLANAR_YUV422:
+        if f in (FRAME_PLANAR_YUV422, FRAME_PLANAR_YUV422P10):
             return [(h, w), (h, w // 2), (h, w // 2)]
+        if f == FRAME_P210:
+            return [(h, w), (h, w // 2, 2)]
+        if f == FRAME_V210:  # dwords: four per group of six pixels
+            return [(h, 4 * ((w + 5) // 6))]
         if f == FRAME_PLANAR_YUV444:
             return [(h, w), (h, w), (h, w)]
         if f in (FRAME_NV12, FRAME_P010):
@@ -97,8 +101,10 @@ class DeviceFrame:
         return [(h, w, 4)]
 
     def plane_dtype(self):
-        """The element type of every plane: 16-bit words for the 10-bit formats, bytes otherwise."""
-        return np.uint16 if self.fmt in (FRAME_P010, FRAME_PLANAR_YUV420P10) else np.uint8
+        """The element type of every plane: 16-bit words for the 10-bit formats (v210: dwords of three codes), bytes otherwise."""
+        if self.fmt == FRAME_V210:
+            return np.uint32
+        return np.uint16 if self.fmt in (FRAME_P010, FRAME_PLANAR_YUV420P10, FRAME_P210, FRAME_PLANAR_YUV422P10) else np.uint8
 
     def upload(self, planes: Sequence[np.ndarray]) -> "DeviceFrame":
         shapes = self.plane_shapes()
@@ -115,8 +121,9 @@ class DeviceFrame:
 
     def pinned_planes(self) -> List[np.ndarray]:
         """Host plane buffers in pinned memory (smr_host_alloc), shaped like this frame's planes; freed with the context."""
-        if self.plane_dtype() == np.uint16:  # (host_array hands out bytes: twice as many per row, seen as words)
-            return [self.ctx.host_array(tuple(s[:-1]) + (2 * s[-1],)).view(np.uint16) for s in self.plane_shapes()]
+        if self.plane_dtype() != np.uint8:  # (host_array hands out bytes: two or four times as many per row, seen as words / dwords)
+            size = np.dtype(self.plane_dtype()).itemsize
+            return [self.ctx.host_array(tuple(s[:-1]) + (size * s[-1],)).view(self.plane_dtype()) for s in self.plane_shapes()]
         return [self.ctx.host_array(s) for s in self.plane_shapes()]
 
     def upload_async(self, pinned: Sequence[np.ndarray]):
@@ -356,7 +363,9 @@ class Context:
         assert len(shapes) == len(planes), "one (pointer, pitch) pair per plane"
         f.surfaces = []
         for i, ((dptr, pitch), shape) in enumerate(zip(planes, shapes)):
-            if f.plane_dtype() == np.uint16:
+            if f.plane_dtype() == np.uint32:
+                pf = PX_RGBA8  # (v210: one dword per texel)
+            elif f.plane_dtype() == np.uint16:
                 pf = PX_RG16 if len(shape) == 3 else PX_R16
             else:
                 pf = PX_RGBA8 if len(shape) == 3 and shape[2] == 4 else PX_RG8 if len(shape) == 3 else PX_R8
