@@ -98,12 +98,38 @@ typedef enum smr_frame_format {
     SMR_FRAME_V210 = 14,              /* one SMR_PX_RGBA8 plane of 4 * ceil(w / 6) texels x h: a texel is one little-endian dword */
 } smr_frame_format;
 
+/* The Y'CbCr matrix of an INPUT frame.  It travels in bits 8 - 11 of smr_frame.format (and of smr_frame_create's `format`); matrix 0 is
+ * the value every format had before, so SMR_FRAME_WITH_MATRIX(f, SMR_MATRIX_BT709) == f and nothing that exists changes meaning.
+ * Accepted on the twelve opaque Y'CbCr formats (every format above but BGRA / ARGB / RGBA).  Refused with SMR_ERR_INVALID: a matrix
+ * value of 3 .. 15, any bit above bit 11, a non-zero matrix on BGRA / ARGB / RGBA, and a non-zero matrix wherever a frame is an OUTPUT
+ * (smr_rgba_to_frame, smr_frame_fill_black, a renderer's output_format).
+ * The value rule: everything up to and including the range step is the format's own — the texel fetch, the 8-bit sub-texel bilinear chroma
+ * sample (the packed formats' snapped fetch), the 10-bit code rule (c * 0.25) / 255, the limited-range division and clamp (none for
+ * YUVJ420).  The last three statements of planar_yuv_to_rgba.wgsl take their four constants from the matrix, each operation rounded to f32:
+ *      r = y + c_rv * (v - 0.5)
+ *      g = y - c_gu * (u - 0.5) - c_gv * (v - 0.5)          (left to right)
+ *      b = y + c_bu * (u - 0.5)
+ * with f32 literals at the reference's four decimals:
+ *      matrix                               c_rv    c_gu    c_gv    c_bu
+ *      BT.709 (the reference)               1.5748  0.1873  0.4681  1.8556
+ *      BT.601 (Kr 0.299, Kb 0.114)          1.4020  0.3441  0.7141  1.7720
+ *      BT.2020 NCL (Kr 0.2627, Kb 0.0593)   1.4746  0.1646  0.5714  1.8814
+ * and the unorm8 store floor(clamp(x) * 255 + 0.5) unchanged.  The node texture and everything behind it are as before.
+ * Not offered: matrices on outputs (outputs stay BT.709); range overrides (full-range NV12 / 4:2:2 / 4:4:4 / 10-bit, limited J420: range
+ * stays what each format defines); BT.2020 constant luminance; transfer functions and primaries (the node stays the gamma-encoded R'G'B'
+ * the reference treats as sRGB: no PQ / HLG, no gamut mapping); the matrix inside the plane-source route (SMR_OPT_PLANE_SOURCE), the f32
+ * k_ingest route and the laboratory fused conversion, which decline tagged frames — those then take the node route, the same bytes. */
+typedef enum smr_color_matrix { SMR_MATRIX_BT709 = 0, SMR_MATRIX_BT601 = 1, SMR_MATRIX_BT2020_NCL = 2 } smr_color_matrix;
+#define SMR_FRAME_WITH_MATRIX(format, m) ((uint32_t)(format) | ((uint32_t)(m) << 8))
+#define SMR_FRAME_BASE_FORMAT(format)    ((uint32_t)(format) & 0xffu)
+#define SMR_FRAME_MATRIX(format)         (((uint32_t)(format) >> 8) & 0xfu)
+
 /* One video frame resident in HBM: up to three pitched plane surfaces.
  * planes[] per format: planar YUV {Y,U,V}; NV12 {Y (R8), UV (RG8)}; P010 / P210 {Y (R16), UV (RG16)}; planar 10-bit {Y,U,V} (R16); packed formats {data}.
  * UYVY/YUYV planes are RGBA8 surfaces of width/2 texels (wgpu/texture/interleaved_yuv422.rs); a v210 plane is an RGBA8 surface of
  * 4 * ceil(width / 6) texels. */
 typedef struct smr_frame {
-    uint32_t format; /* smr_frame_format */
+    uint32_t format; /* smr_frame_format, for an input frame optionally | smr_color_matrix << 8 (SMR_FRAME_WITH_MATRIX) */
     uint32_t width;
     uint32_t height;
     smr_surface *planes[3];
@@ -909,7 +935,10 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      SMR_KERNEL_INGEST_MFMA_WG, counts SMR_KERNEL_FRAME_TO_RGBA_420.  smr_text_params moved in front of the font-book entry points.  The
  *      SMR_CONVERT_GENERAL / SMR_DISABLE_FUSED / SMR_COMPOSE_SELECT environment knobs are smr_ctx_set_option options in a product build
  *      (the environment is read by laboratory builds only).
- *      Added since, without a new version (additions only: nothing a version-2 host calls changed): SMR_KERNEL_MOVE_RECTS (counter slot 8),
+ *      Added since, without a new version (additions only: nothing a version-2 host calls changed) — the latest first: input colour
+ *      matrices (smr_color_matrix, SMR_FRAME_WITH_MATRIX / _BASE_FORMAT / _MATRIX: bits 8 - 11 of smr_frame.format, which every version-2
+ *      host leaves zero = BT.709; no struct changed, no kernel counter slot was added, no untagged frame converts differently); then, oldest
+ *      first: SMR_KERNEL_MOVE_RECTS (counter slot 8),
  *      SMR_KERNEL_INGEST_WAVE_DIRECT (counter slot 9),
  *      smr_renderer_add_shard, smr_renderer_input_ctx; user shaders (smr_shader_program_*, smr_user_shader,
  *      smr_renderer_register_shader_source / _program); in the user-shader language, no new C symbol: the affine vertex stage

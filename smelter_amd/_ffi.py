@@ -19,6 +19,9 @@ PX_R16, PX_RG16 = 4, 5  # 16-bit words: the planes of the 10-bit frame formats
  FRAME_NV12, FRAME_BGRA, FRAME_ARGB, FRAME_RGBA) = range(10)
 FRAME_P010, FRAME_PLANAR_YUV420P10 = 10, 11  # 10-bit 4:2:0, limited range, input only (code = word >> 6 | word & 0x3ff)
 FRAME_PLANAR_YUV422P10, FRAME_P210, FRAME_V210 = 12, 13, 14  # 10-bit 4:2:2, limited range, input only (word & 0x3ff | word >> 6 | three codes per dword)
+# smr_color_matrix: the Y'CbCr matrix of an INPUT frame, bits 8 - 11 of its format (include/smr.h); 0 = BT.709 = every format's value as it was
+MATRIX_BT709, MATRIX_BT601, MATRIX_BT2020_NCL = 0, 1, 2
+
 MAX_MASKS = 20
 NO_SOURCE = 0xFFFFFFFF
 SOURCE_NONE, SOURCE_SURFACE, SOURCE_FRAME, SOURCE_OPAQUE_SURFACE = 0, 1, 2, 3
@@ -149,6 +152,22 @@ class OutputFrame(C.Structure):
 
 
 _lib = None
+
+
+# the split of smr_frame.format (include/smr.h: SMR_FRAME_WITH_MATRIX / _BASE_FORMAT / _MATRIX)
+def frame_format(fmt: int, matrix: int = MATRIX_BT709) -> int:
+    """SMR_FRAME_WITH_MATRIX: the format value of an input frame of base format `fmt` whose Y'CbCr matrix is `matrix`."""
+    return int(fmt) | (int(matrix) << 8)
+
+
+def frame_base_format(fmt: int) -> int:
+    """SMR_FRAME_BASE_FORMAT: what decides a frame's planes."""
+    return int(fmt) & 0xff
+
+
+def frame_matrix(fmt: int) -> int:
+    """SMR_FRAME_MATRIX"""
+    return (int(fmt) >> 8) & 0xf
 
 
 def load():

@@ -568,6 +568,8 @@ int run_gather(smr_renderer *r, Gather &g) {
 int stage_remote_frame(smr_renderer *r, Output &o, Source &s, Gather &g) {
     ShardSlot &slot = o.l->shard[o.l->flip][s.node];
     const smr_frame *f = s.frame;
+    // (an input may change its colour matrix from one frame to the next: the planes are the base format's, the stand-in just takes the new tag)
+    if (slot.have_staged && frame_base_format(slot.staged.format) == frame_base_format(f->format) && !frame_format_tag_error(f->format)) slot.staged.format = f->format;
     if (slot.have_staged && (slot.staged.format != f->format || slot.staged.width != f->width || slot.staged.height != f->height)) {
         sync_lanes(r);  // (an owner may still be writing it)
         smr_frame_destroy(r->lane_ctx[0], &slot.staged);
@@ -1442,6 +1444,9 @@ static int draw_text_nodes(smr_renderer *r, Output &o) {
 SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, uint32_t width, uint32_t height, uint32_t output_format,
                                       const char *scene_json) {
     if (!r || !output_id || !scene_json || !width || !height) return fail(r, -1, "smr_renderer_update_scene: null argument");
+    if (output_format > 0xffu)  // (the previous scene of this output stays active, as after every refusal here)
+        return fail(r, -1, frame_format_tag_error(output_format) ? "smr_renderer_update_scene: output format has bits outside a colour matrix the library knows; and an output format carries no colour matrix at all"
+                                                                  : "smr_renderer_update_scene: output format carries a colour matrix: outputs are BT.709, a matrix applies to input frames only");
     if (output_format != SMR_FRAME_PLANAR_YUV420 && output_format != SMR_FRAME_PLANAR_YUV422 && output_format != SMR_FRAME_PLANAR_YUV444 &&
         output_format != SMR_FRAME_NV12 && output_format != SMR_FRAME_RGBA)
         return fail(r, -1, frame_format_is_hi_depth(output_format) ? "smr_renderer_update_scene: the 10-bit frame formats are input only; output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12 or RGBA"

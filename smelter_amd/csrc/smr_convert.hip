@@ -21,7 +21,8 @@ constexpr int BLOCK = 256;
 
 // kind: 0 planar (3 R8 planes), 1 NV12 (R8 + RG8)
 template <int KIND>
-__global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up, SurfView vp, SurfView dst, int full) {
+__global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up, SurfView vp, SurfView dst, int full, u32 matrix) {
+    const SmrMatrixCoef C = smr_matrix_coef(matrix);  // (uniform: the frame's smr_color_matrix)
     const int groups = (dst.w + 3) >> 2;
     const int gx = blockIdx.x * BLOCK + threadIdx.x;
     const int y = blockIdx.y;
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up,
             uu = sample_plane_bilinear(up, 2, 0, tu, tv);
             vv = sample_plane_bilinear(up, 2, 1, tu, tv);
         }
-        px[i] = yuv_to_rgb_px(yy, uu, vv, full != 0);
+        px[i] = yuv_to_rgb_px(yy, uu, vv, full != 0, C);
     }
     u8 *row = dst.ptr + (size_t)y * dst.pitch;
     if (x0 + 3 < dst.w) {
@@ -56,7 +57,8 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up,
 // The 10-bit twin (smr_convert_hi.h), statement for statement with the 16-bit fetch: any geometry — odd sizes, widths below 8, 1x1 with
 // placeholder chroma planes.  kind: 0 planar 10-bit (3 R16 planes, code = word & 0x3ff), 1 P010 (R16 + RG16, code = word >> 6); limited range.
 template <int KIND>
-__global__ __launch_bounds__(BLOCK) void k_yuv_hi_to_rgba(SurfView yp, SurfView up, SurfView vp, SurfView dst) {
+__global__ __launch_bounds__(BLOCK) void k_yuv_hi_to_rgba(SurfView yp, SurfView up, SurfView vp, SurfView dst, u32 matrix) {
+    const SmrMatrixCoef C = smr_matrix_coef(matrix);
     const int groups = (dst.w + 3) >> 2;
     const int gx = blockIdx.x * BLOCK + threadIdx.x;
     const int y = blockIdx.y;
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_hi_to_rgba(SurfView yp, SurfView 
             uu = sample_plane_bilinear_hi<true>(up, 2, 0, tu, tv);
             vv = sample_plane_bilinear_hi<true>(up, 2, 1, tu, tv);
         }
-        px[i] = yuv_to_rgb_px(yy, uu, vv, false);
+        px[i] = yuv_to_rgb_px(yy, uu, vv, false, C);
     }
     u8 *row = dst.ptr + (size_t)y * dst.pitch;
     if (x0 + 3 < dst.w) {
@@ -92,14 +94,14 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_hi_to_rgba(SurfView yp, SurfView 
 // (w / 2) x h chroma plane is all that differs.  This is v210 (smr_convert_hi422.h): k_interleaved422_to_rgba's shape, one pixel per thread,
 // luma Y[x] and the chroma of pair x / 2 for every width (include/smr.h), then the limited-range conversion.
 template <int LAYOUT>
-__global__ __launch_bounds__(BLOCK) void k_yuv422_hi_to_rgba_any(SurfView src, SurfView dst) {
+__global__ __launch_bounds__(BLOCK) void k_yuv422_hi_to_rgba_any(SurfView src, SurfView dst, u32 matrix) {
     static_assert(LAYOUT == CV422_V210, "planar 10-bit and P210 are served by k_yuv_hi_to_rgba");
     const int x = blockIdx.x * BLOCK + threadIdx.x;
     const int y = blockIdx.y;
     if (x >= dst.w) return;
     u32 yc, cb, cr;
     cv210_pixel_codes(src.ptr + (size_t)y * src.pitch, x, yc, cb, cr);
-    *(u32 *)(dst.ptr + (size_t)y * dst.pitch + (size_t)x * 4) = yuv_to_rgb_px(cvhi_unorm_of_code(yc), cvhi_unorm_of_code(cb), cvhi_unorm_of_code(cr), false);
+    *(u32 *)(dst.ptr + (size_t)y * dst.pitch + (size_t)x * 4) = yuv_to_rgb_px(cvhi_unorm_of_code(yc), cvhi_unorm_of_code(cb), cvhi_unorm_of_code(cr), false, smr_matrix_coef(matrix));
 }
 
 // The same pass for planar 4:2:0 (limited or full range), 4:2:2, 4:4:4 and NV12 frames, several frames per launch: what k_yuv_to_rgba
@@ -113,6 +115,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv422_hi_to_rgba_any(SurfView src, S
 // (ConvJob / ConvBatch: smr_convert_420.h)
 __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba_batch(const ConvBatch B) {
     const ConvJob &J = B.j[blockIdx.z];
+    const SmrMatrixCoef C = smr_matrix_coef((u32)J.matrix);  // (uniform: the job's smr_color_matrix)
     const int g = blockIdx.x * 64 + (threadIdx.x & 63), p = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int w = J.dst.w, h = J.dst.h, cw = J.sx ? w >> 1 : w, ch = J.sy ? h >> 1 : h;
     if (4 * g >= w || 2 * p >= h) return;
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba_batch(const ConvBatch B) 
                 const u32 c0 = d & 0xffu, c1 = (d >> 8) & 0xffu, c2 = (d >> 16) & 0xffu, c3 = d >> 24;
                 const u32 ub = J.packed == 1 ? c0 : c1, vb = J.packed == 1 ? c2 : c3;
                 const u32 yb = J.packed == 1 ? ((i & 1) ? c3 : c1) : ((i & 1) ? c2 : c0);
-                px[i] = yuv_to_rgb_px_cr(unorm_of_byte(yb), unorm_of_byte(ub), unorm_of_byte(vb), false);
+                px[i] = yuv_to_rgb_px_cr(unorm_of_byte(yb), unorm_of_byte(ub), unorm_of_byte(vb), false, C);
             }
             u8 *row = J.dst.ptr + ((u32)y * J.dst.pitch + 16u * (u32)g);
             if (4 * g + 3 < w) {
@@ -246,7 +249,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba_batch(const ConvBatch B) 
             float uu = r == 0 ? H[0][0][i] * 0.25f + H[0][1][i] * 0.75f : H[0][1][i] * 0.75f + H[0][2][i] * 0.25f;
             float vv = r == 0 ? H[1][0][i] * 0.25f + H[1][1][i] * 0.75f : H[1][1][i] * 0.75f + H[1][2][i] * 0.25f;
             if (!J.sy) { uu = H[0][r][i]; vv = H[1][r][i]; }
-            px[i] = yuv_to_rgb_px_cr(yy, uu, vv, J.full != 0);
+            px[i] = yuv_to_rgb_px_cr(yy, uu, vv, J.full != 0, C);
         }
         u8 *row = J.dst.ptr + ((u32)y * J.dst.pitch + 16u * (u32)g);
         if (4 * g + 3 < w) {
@@ -258,7 +261,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba_batch(const ConvBatch B) 
 }
 
 // interleaved_{uyvy,yuyv}_to_rgba.wgsl:24-62. src is the (w/2) x h RGBA8 packed texture.
-__global__ __launch_bounds__(BLOCK) void k_interleaved422_to_rgba(SurfView src, SurfView dst, int order) {
+__global__ __launch_bounds__(BLOCK) void k_interleaved422_to_rgba(SurfView src, SurfView dst, int order, u32 matrix) {
     const int x = blockIdx.x * BLOCK + threadIdx.x;
     const int y = blockIdx.y;
     if (x >= dst.w) return;
@@ -275,7 +278,7 @@ __global__ __launch_bounds__(BLOCK) void k_interleaved422_to_rgba(SurfView src, 
     float yy, uu, vv;
     if (order == 0) { uu = c0; vv = c2; yy = (x_pos % 2 != 0) ? c3 : c1; }
     else            { uu = c1; vv = c3; yy = (x_pos % 2 != 0) ? c2 : c0; }
-    *(u32 *)(dst.ptr + (size_t)y * dst.pitch + (size_t)x * 4) = yuv_to_rgb_px(yy, uu, vv, false);
+    *(u32 *)(dst.ptr + (size_t)y * dst.pitch + (size_t)x * 4) = yuv_to_rgb_px(yy, uu, vv, false, smr_matrix_coef(matrix));
 }
 
 // bgra_to_rgba.wgsl:24-28 (sample.bgra) / argb_to_rgba.wgsl:24-28 (sample.argb): byte permutes.
@@ -391,7 +394,9 @@ extern "C" __attribute__((visibility("default"))) int smr_debug_convert_stamps(u
 }
 #endif
 
-template <bool NV>
+// MATRIX: the smr_color_matrix of every job of the launch (the host queues per matrix) — a compile-time property, so that the BT.709 launch is
+// the code it was before the matrices and the others are the same instruction stream with four other literals.
+template <bool NV, int MATRIX = SMR_MATRIX_BT709>
 #ifndef SMR_CONVERT_MIN_WAVES
 #define SMR_CONVERT_MIN_WAVES 1  // waves per SIMD the converter's register allocation must leave room for (A/B knob: 8 = at most 64 registers, so that more of its waves fit beside another lane's resampler)
 #endif
@@ -413,7 +418,7 @@ __global__ __launch_bounds__(BLOCK, SMR_CONVERT_MIN_WAVES) void k_yuv420_to_rgba
     s_nlut[threadIdx.x & 255] = unorm_of_byte(threadIdx.x & 255u);
     __syncthreads();
     CV_STAMP(st, 1, "s_nop 0");
-    cv420_share<NV>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, lane, s_ylut, s_nlut, st);
+    cv420_share<NV, false, MATRIX>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, lane, s_ylut, s_nlut, st);
 #ifdef CV_TIMING
     st = g_cv_stamps[(blockIdx.x * 4u + (threadIdx.x >> 6)) & 32767u];
 #endif
@@ -427,7 +432,7 @@ __global__ __launch_bounds__(BLOCK, SMR_CONVERT_MIN_WAVES) void k_yuv420_to_rgba
 // The same for frames with a chroma plane whose rows fill its pitch and that the library did not allocate (conv_420_ok: a wrapped decoder
 // surface with tight rows): cv420_load_chroma's TIGHT build requests nothing behind a window's last column.  A kernel of its own, so that the
 // plain one stays the instruction stream it was measured as.
-template <bool NV>
+template <bool NV, int MATRIX = SMR_MATRIX_BT709>
 __global__ __launch_bounds__(BLOCK) void k_yuv420_to_rgba_tight(const ConvBatch B) {
     __shared__ float s_ylut[256], s_nlut[256];
 #ifdef SMR_PRIO_CONVERT
@@ -446,7 +451,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv420_to_rgba_tight(const ConvBatch 
     s_nlut[threadIdx.x & 255] = unorm_of_byte(threadIdx.x & 255u);
     __syncthreads();
     CV_STAMP(st, 1, "s_nop 0");
-    cv420_share<NV, true>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, lane, s_ylut, s_nlut, st);
+    cv420_share<NV, true, MATRIX>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, lane, s_ylut, s_nlut, st);
 #ifdef CV_TIMING
     st = g_cv_stamps[(blockIdx.x * 4u + (threadIdx.x >> 6)) & 32767u];
 #endif
@@ -459,7 +464,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv420_to_rgba_tight(const ConvBatch 
 
 // 10-bit 4:2:0 frames the block converter takes (smr_convert_hi.h, conv_hi_mode): the same persistent launch cut into equal shares, with two
 // 1024-entry tables (the code's unorm value, its luma range expansion) built per workgroup with the operations themselves — 8 KB of LDS, the four
-// workgroups a CU holds at 101 registers stay far below its 160 KB.  One kernel per format, no plain / tight pair: no load leaves a plane row's bytes.
+// workgroups a CU is given (83 / 84 registers: DESIGN.md 3l) stay far below its 160 KB.  One kernel per format, no plain / tight pair: no load leaves a plane row's bytes.
 template <bool P010>
 __global__ __launch_bounds__(BLOCK) void k_yuv420_hi_to_rgba(const ConvBatch B) {
     __shared__ float s_ylut[CVHI_CODES], s_ulut[CVHI_CODES];
@@ -577,14 +582,15 @@ static int smr_frame_to_rgba_general(smr_ctx *ctx, const smr_frame *in, smr_surf
 // k_yuv_to_rgba_batch's frames: planar 4:2:0 / 4:2:2 / 4:4:4 and NV12 whose subsampled axes are even (chroma planes exactly half), within the
 // size the coordinate argument holds for
 static bool conv_batchable(const smr_ctx *ctx, const smr_frame *in) {
+    const u32 fmt = frame_base_format(in->format);  // (the colour matrix changes no route)
     if (in->width < 2 || in->height < 2 || in->width > 16384 || in->height > 16384 || ctx->convert_impl == SMR_CONVERT_GENERAL) return false;
-    if (in->format == SMR_FRAME_UYVY422 || in->format == SMR_FRAME_YUYV422)
+    if (fmt == SMR_FRAME_UYVY422 || fmt == SMR_FRAME_YUYV422)
         return in->width % 2 == 0 && in->width >= 8 && in->planes[0] && (in->planes[0]->pitch & 3u) == 0 && (((uintptr_t)in->planes[0]->ptr) & 3) == 0;
-    if (in->format == SMR_FRAME_BGRA || in->format == SMR_FRAME_ARGB)
+    if (fmt == SMR_FRAME_BGRA || fmt == SMR_FRAME_ARGB)
         return in->planes[0] && (in->planes[0]->pitch & 15u) == 0 && (((uintptr_t)in->planes[0]->ptr) & 15) == 0;
-    const bool nv = in->format == SMR_FRAME_NV12;
-    const bool sx = in->format != SMR_FRAME_PLANAR_YUV444, sy = in->format == SMR_FRAME_PLANAR_YUV420 || in->format == SMR_FRAME_PLANAR_YUVJ420 || nv;
-    if (in->format > SMR_FRAME_PLANAR_YUVJ420 && !nv) return false;  // (BGRA / ARGB / RGBA: byte permutes of their own)
+    const bool nv = fmt == SMR_FRAME_NV12;
+    const bool sx = fmt != SMR_FRAME_PLANAR_YUV444, sy = fmt == SMR_FRAME_PLANAR_YUV420 || fmt == SMR_FRAME_PLANAR_YUVJ420 || nv;
+    if (fmt > SMR_FRAME_PLANAR_YUVJ420 && !nv) return false;  // (BGRA / ARGB / RGBA: byte permutes of their own)
     if ((sx && in->width % 2) || (sy && in->height % 2)) return false;
     return in->planes[0] && in->planes[1] && (nv || in->planes[2]);
 }
@@ -595,9 +601,10 @@ static bool conv_batchable(const smr_ctx *ctx, const smr_frame *in) {
 // or the 16 bytes every allocation ends with (SMR_SURFACE_TAIL) — a wrapped one is read inside its rows' bytes only: it takes
 // k_yuv420_to_rgba_tight, which requests nothing behind a window's last column (tight rows — a decoder's pitch == bytes per row — or wide ones).  -> 0: not a frame for the block converter | 1: the plain kernel | 2: the tight one
 static int conv_420_mode(const smr_ctx *ctx, const smr_frame *in) {
+    const u32 fmt = frame_base_format(in->format);  // (the colour matrix changes no route)
     if (ctx->convert_impl != SMR_CONVERT_AUTO) return 0;
-    const bool nv = in->format == SMR_FRAME_NV12;
-    if (in->format != SMR_FRAME_PLANAR_YUV420 && in->format != SMR_FRAME_PLANAR_YUVJ420 && !nv) return 0;
+    const bool nv = fmt == SMR_FRAME_NV12;
+    if (fmt != SMR_FRAME_PLANAR_YUV420 && fmt != SMR_FRAME_PLANAR_YUVJ420 && !nv) return 0;
     if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return 0;
     auto dwords = [](const smr_surface *s) { return s && (s->pitch & 3u) == 0 && (((uintptr_t)s->ptr) & 3) == 0; };
     if (!dwords(in->planes[0]) || !dwords(in->planes[1]) || (!nv && !dwords(in->planes[2]))) return 0;
@@ -618,8 +625,9 @@ static bool conv_420_ok(const smr_ctx *ctx, const smr_frame *in) { return conv_4
 // one 8-byte load at 8 g: the Y plane's pointer and pitch are 8-byte aligned; the chroma loads are dwords: dword-aligned.  Nothing else: the
 // kernel requests no byte outside a row's own bytes, so owned and wrapped planes, wide and tight rows are one case.
 static bool conv_hi_mode(const smr_ctx *ctx, const smr_frame *in) {
-    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth(in->format) || frame_format_is_hi_depth_422(in->format)) return false;
-    const bool nv = in->format == SMR_FRAME_P010;
+    const u32 fmt = frame_base_format(in->format);  // (the colour matrix changes no route)
+    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth(fmt) || frame_format_is_hi_depth_422(fmt)) return false;
+    const bool nv = fmt == SMR_FRAME_P010;
     if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return false;
     auto aligned = [](const smr_surface *s, uintptr_t a) { return s && (s->pitch & (a - 1)) == 0 && (((uintptr_t)s->ptr) & (a - 1)) == 0; };
     if (!aligned(in->planes[0], 8) || !aligned(in->planes[1], 4) || (!nv && !aligned(in->planes[2], 4))) return false;
@@ -632,12 +640,13 @@ static bool conv_hi_mode(const smr_ctx *ctx, const smr_frame *in) {
 // pointer and pitch are 8-byte aligned; the chroma loads are dwords: dword-aligned.  Nothing else: the kernel requests no byte outside a row's
 // own bytes, so owned and wrapped planes, wide and tight rows (a capture card's stride among them) are one case.
 static bool conv_hi422_mode(const smr_ctx *ctx, const smr_frame *in) {
-    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth_422(in->format)) return false;
+    const u32 fmt = frame_base_format(in->format);  // (the colour matrix changes no route)
+    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth_422(fmt)) return false;
     if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return false;
     auto aligned = [](const smr_surface *s, uintptr_t a) { return s && (s->pitch & (a - 1)) == 0 && (((uintptr_t)s->ptr) & (a - 1)) == 0; };
     if (!aligned(in->planes[0], 8)) return false;
-    if (in->format == SMR_FRAME_V210) return in->planes[0]->pitch >= 16u * ((in->width + 5u) / 6u);
-    const bool nv = in->format == SMR_FRAME_P210;
+    if (fmt == SMR_FRAME_V210) return in->planes[0]->pitch >= 16u * ((in->width + 5u) / 6u);
+    const bool nv = fmt == SMR_FRAME_P210;
     if (!aligned(in->planes[1], 4) || (!nv && !aligned(in->planes[2], 4))) return false;
     const u32 crow = nv ? 2u * in->width : in->width;  // bytes of a chroma row: w / 2 columns of 4 (2) bytes
     return in->planes[0]->pitch >= 2u * in->width && in->planes[1]->pitch >= crow && (nv || in->planes[2]->pitch >= crow);
@@ -647,8 +656,18 @@ bool smr_conv_rgb12_ok(const smr_ctx *ctx, const smr_frame *in) {
     return in && (conv_420_ok(ctx, in) || conv_hi_mode(ctx, in) || conv_hi422_mode(ctx, in)) && 3u * in->width <= 7682u * 2u;
 }
 
-// smr_frame_to_rgba for several frames: one launch for every 16 frames of a kind (k_yuv420_to_rgba planar / NV12, k_yuv_to_rgba_batch), the
-// others one by one.  Everything queued is launched before the call returns, errors included.
+// k_yuv420_to_rgba / _tight of one matrix: kind 1 planar | 2 NV12 | 3 tight planar | 4 tight NV12
+template <int MATRIX>
+static void launch_cv420(int kind, u32 blocks, u32 lds_pad, hipStream_t stream, const ConvBatch &B) {
+    if (kind == 1) hipLaunchKernelGGL((k_yuv420_to_rgba<false, MATRIX>), dim3(blocks), dim3(BLOCK), lds_pad, stream, B);
+    else if (kind == 2) hipLaunchKernelGGL((k_yuv420_to_rgba<true, MATRIX>), dim3(blocks), dim3(BLOCK), lds_pad, stream, B);
+    else if (kind == 3) hipLaunchKernelGGL((k_yuv420_to_rgba_tight<false, MATRIX>), dim3(blocks), dim3(BLOCK), lds_pad, stream, B);
+    else hipLaunchKernelGGL((k_yuv420_to_rgba_tight<true, MATRIX>), dim3(blocks), dim3(BLOCK), lds_pad, stream, B);
+}
+
+// smr_frame_to_rgba for several frames: one launch for every 16 frames of a kind (k_yuv420_to_rgba planar / NV12 — per colour matrix, whose
+// instantiations differ: a batch that mixes matrices makes one launch per matrix present —, the 10-bit block converters, k_yuv_to_rgba_batch),
+// the others one by one.  Everything queued is launched before the call returns, errors included.
 int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surface *const *nodes, u32 n, const u8 *rgb12) {
     if (!ctx || (n && (!in || !nodes))) return SMR_ERR_INVALID;
     // validate first, enqueue afterwards: no frame is left half-queued by a bad one behind it
@@ -667,13 +686,17 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         u32 nb = 0;
         int mw = 0, mh = 0;
     };
-    constexpr int NQ = 10;
-    // 0: k_yuv_to_rgba_batch | 1: k_yuv420_to_rgba planar | 2: ... NV12 | 3, 4: k_yuv420_to_rgba_tight planar, NV12 | 5, 6: k_yuv420_hi_to_rgba planar
-    // 10-bit, P010 | 7, 8, 9: k_yuv422_hi_to_rgba planar 10-bit 4:2:2, P210, v210
+    constexpr int NK = 10, NQ = NK + 4 * (SMR_MATRIX_COUNT - 1);
+    // kernel kinds — 0: k_yuv_to_rgba_batch | 1: k_yuv420_to_rgba planar | 2: ... NV12 | 3, 4: k_yuv420_to_rgba_tight planar, NV12 | 5, 6: k_yuv420_hi_to_rgba planar
+    // 10-bit, P010 | 7, 8, 9: k_yuv422_hi_to_rgba planar 10-bit 4:2:2, P210, v210.
+    // Queues — per (kind, matrix) for kinds 1 - 4, whose matrix is a template parameter of the kernel: queue `kind` holds the BT.709 jobs (an
+    // all-709 batch makes the launches it always made), queue NK + 4 (m - 1) + kind - 1 those of matrix m; a batch that mixes matrices makes
+    // one launch per matrix present.  The other kinds read the matrix from the job: one queue each.
     Queue q[NQ];
-    auto flush = [&](int k) -> int {
-        Queue &Q = q[k];
+    auto flush = [&](int qi) -> int {
+        Queue &Q = q[qi];
         if (!Q.nb) return SMR_OK;
+        const int k = qi < NK ? qi : 1 + (qi - NK) % 4, m = qi < NK ? 0 : 1 + (qi - NK) / 4;
         StageScope scope(ctx, SMR_STAGE_INGEST);
         ctx->kernel_launches[SMR_KERNEL_FRAME_TO_RGBA]++;  // (per launch)
         if (k != 0) ctx->kernel_launches[SMR_KERNEL_FRAME_TO_RGBA_420]++;
@@ -689,11 +712,13 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
             // kernel runs beside the other lane's kernels; configs[2] (8 640 units: 1.4 per wave at six) gains 2 % at five, configs[3]
             // (64 800 units) loses 1 % (profiles/r06_sensitivity.txt section 9)
             const int want = ctx->convert_wg_per_cu > 0 ? ctx->convert_wg_per_cu : (total >= 32768u ? 6 : 5);
-            // (the 10-bit kernels hold 101 registers: four workgroups per CU are resident, a fifth would only queue behind them)
+            // (the 4:2:0 10-bit kernels: four workgroups per CU, the number they were measured at when they held 101 registers and a
+            //  fifth could only queue; with the matrix coefficients in scalar registers they hold 83 / 84 and a fifth would fit — kept at
+            //  four until a fifth is measured: not on the benchmark's path)
             u32 per_cu = k >= 5 ? 4u : (u32)(want > 6 ? 6 : want);
             if (k >= 7) {  // the 4:2:2 kernels: as many workgroups per CU as the kernel's own registers and LDS keep resident (asked once per context)
                 const void *kern = k == 7 ? (const void *)k_yuv422_hi_to_rgba<CV422_PLANAR> : k == 8 ? (const void *)k_yuv422_hi_to_rgba<CV422_P210> : (const void *)k_yuv422_hi_to_rgba<CV422_V210>;
-                int resident = 0;
+                int resident = 0;  // (key 2000 + k: one instantiation per kind — these kernels read the matrix from the job, so the key need not tell matrices apart)
                 for (auto &o : ctx->mfma_occupancy)
                     if (o.kernel == 2000 + k && o.lds == 0) resident = o.per_cu;
                 if (!resident) {
@@ -709,15 +734,16 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
             const u32 bands = cv420_plan(Q.B, (int)Q.nb, blocks * 4u);
             if (blocks < (bands < 8u ? bands : 8u)) blocks = bands < 8u ? bands : 8u;  // (every XCD that owns a band runs a workgroup)
             const u32 lds_pad = ctx->convert_lds_pad;
-            if (k == 1) hipLaunchKernelGGL(k_yuv420_to_rgba<false>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
-            else if (k == 2) hipLaunchKernelGGL(k_yuv420_to_rgba<true>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
-            else if (k == 3) hipLaunchKernelGGL(k_yuv420_to_rgba_tight<false>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
+            if (k <= 4) {
+                if (m == SMR_MATRIX_BT601) launch_cv420<SMR_MATRIX_BT601>(k, blocks, lds_pad, ctx->stream, Q.B);
+                else if (m == SMR_MATRIX_BT2020_NCL) launch_cv420<SMR_MATRIX_BT2020_NCL>(k, blocks, lds_pad, ctx->stream, Q.B);
+                else launch_cv420<SMR_MATRIX_BT709>(k, blocks, lds_pad, ctx->stream, Q.B);
+            }
             else if (k == 5) hipLaunchKernelGGL(k_yuv420_hi_to_rgba<false>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
             else if (k == 6) hipLaunchKernelGGL(k_yuv420_hi_to_rgba<true>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
             else if (k == 7) hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_PLANAR>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
             else if (k == 8) hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_P210>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
-            else if (k == 9) hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_V210>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
-            else hipLaunchKernelGGL(k_yuv420_to_rgba_tight<true>, dim3(blocks), dim3(BLOCK), lds_pad, ctx->stream, Q.B);
+            else hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_V210>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
         }
         Q.nb = 0; Q.mw = 0; Q.mh = 0;
         SMR_HIP(ctx, hipGetLastError());
@@ -731,10 +757,11 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
     };
     for (u32 i = 0; i < n; i++) {
         const bool c12 = rgb12 && rgb12[i];
+        const u32 fmt = frame_base_format(in[i]->format), matrix = frame_matrix(in[i]->format);
         const bool aligned16 = c12 || ((((uintptr_t)nodes[i]->ptr) & 15) == 0 && (nodes[i]->pitch & 15u) == 0);  // (the block kernels store 16 B)
-        const bool nv = in[i]->format == SMR_FRAME_NV12 || in[i]->format == SMR_FRAME_P010 || in[i]->format == SMR_FRAME_P210;
+        const bool nv = fmt == SMR_FRAME_NV12 || fmt == SMR_FRAME_P010 || fmt == SMR_FRAME_P210;
         const int mode = conv_420_mode(ctx, in[i]);
-        const int k = !aligned16 ? -1 : conv_hi422_mode(ctx, in[i]) ? (in[i]->format == SMR_FRAME_V210 ? 9 : nv ? 8 : 7) : conv_hi_mode(ctx, in[i]) ? (nv ? 6 : 5) : mode ? (nv ? 2 : 1) + (mode == 2 ? 2 : 0) : conv_batchable(ctx, in[i]) ? 0 : -1;
+        const int k = !aligned16 ? -1 : conv_hi422_mode(ctx, in[i]) ? (fmt == SMR_FRAME_V210 ? 9 : nv ? 8 : 7) : conv_hi_mode(ctx, in[i]) ? (nv ? 6 : 5) : mode ? (nv ? 2 : 1) + (mode == 2 ? 2 : 0) : conv_batchable(ctx, in[i]) ? 0 : -1;
         if (k < 0) {
             if (int rc = smr_frame_to_rgba_general(ctx, in[i], nodes[i])) {
                 (void)flush_all();
@@ -742,25 +769,27 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
             }
             continue;
         }
-        Queue &Q = q[k];
+        const int qi = k >= 1 && k <= 4 && matrix ? NK + 4 * ((int)matrix - 1) + k - 1 : k;
+        Queue &Q = q[qi];
         ConvJob &J = Q.B.j[Q.nb++];
-        const bool packed = in[i]->format == SMR_FRAME_UYVY422 || in[i]->format == SMR_FRAME_YUYV422 || in[i]->format == SMR_FRAME_BGRA || in[i]->format == SMR_FRAME_ARGB ||
-                            in[i]->format == SMR_FRAME_V210;
+        J.matrix = (int)matrix;
+        const bool packed = fmt == SMR_FRAME_UYVY422 || fmt == SMR_FRAME_YUYV422 || fmt == SMR_FRAME_BGRA || fmt == SMR_FRAME_ARGB ||
+                            fmt == SMR_FRAME_V210;
         J.yp = view_of(in[i]->planes[0]);
         J.up = packed ? J.yp : view_of(in[i]->planes[1]);
         J.vp = packed || nv ? J.up : view_of(in[i]->planes[2]);
-        J.packed = in[i]->format == SMR_FRAME_UYVY422 ? 1 : in[i]->format == SMR_FRAME_YUYV422 ? 2 : in[i]->format == SMR_FRAME_BGRA ? 3 : in[i]->format == SMR_FRAME_ARGB ? 4 : 0;
+        J.packed = fmt == SMR_FRAME_UYVY422 ? 1 : fmt == SMR_FRAME_YUYV422 ? 2 : fmt == SMR_FRAME_BGRA ? 3 : fmt == SMR_FRAME_ARGB ? 4 : 0;
         J.dst = view_of(nodes[i]);
         J.rgb12 = c12 ? 1 : 0;
         if (c12) J.dst.w = (int)in[i]->width;  // (in pixels: the kernel's geometry; the rows hold 3 w bytes)
-        J.full = in[i]->format == SMR_FRAME_PLANAR_YUVJ420 ? 1 : 0;
+        J.full = fmt == SMR_FRAME_PLANAR_YUVJ420 ? 1 : 0;
         J.nv = nv ? 1 : 0;
-        J.sx = in[i]->format != SMR_FRAME_PLANAR_YUV444 ? 1 : 0;
-        J.sy = (in[i]->format == SMR_FRAME_PLANAR_YUV420 || in[i]->format == SMR_FRAME_PLANAR_YUVJ420 || in[i]->format == SMR_FRAME_PLANAR_YUV420P10 || (nv && in[i]->format != SMR_FRAME_P210)) ? 1 : 0;
+        J.sx = fmt != SMR_FRAME_PLANAR_YUV444 ? 1 : 0;
+        J.sy = (fmt == SMR_FRAME_PLANAR_YUV420 || fmt == SMR_FRAME_PLANAR_YUVJ420 || fmt == SMR_FRAME_PLANAR_YUV420P10 || (nv && fmt != SMR_FRAME_P210)) ? 1 : 0;
         Q.mw = (int)in[i]->width > Q.mw ? (int)in[i]->width : Q.mw;
         Q.mh = (int)in[i]->height > Q.mh ? (int)in[i]->height : Q.mh;
         if (Q.nb == MAX_CONV_JOBS)
-            if (int rc = flush(k)) {
+            if (int rc = flush(qi)) {
                 (void)flush_all();
                 return rc;
             }
@@ -783,7 +812,8 @@ static int smr_frame_to_rgba_general(smr_ctx *ctx, const smr_frame *in, smr_surf
     ctx->kernel_launches[SMR_KERNEL_FRAME_TO_RGBA]++;
     SurfView dst = view_of(node);
     const int w = (int)in->width, h = (int)in->height;
-    switch (in->format) {
+    const u32 fmt = frame_base_format(in->format), matrix = frame_matrix(in->format);  // (smr_validate_frame has checked the tag)
+    switch (fmt) {
     case SMR_FRAME_PLANAR_YUV420:
     case SMR_FRAME_PLANAR_YUV422:
     case SMR_FRAME_PLANAR_YUV444:
@@ -792,51 +822,51 @@ static int smr_frame_to_rgba_general(smr_ctx *ctx, const smr_frame *in, smr_surf
         SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]), vp = view_of(in->planes[2]);
         // planes keep a 1x1 placeholder when the logical chroma size is 0; sample with the logical size
         hipLaunchKernelGGL(k_yuv_to_rgba<0>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, vp, dst,
-                           in->format == SMR_FRAME_PLANAR_YUVJ420 ? 1 : 0);
+                           fmt == SMR_FRAME_PLANAR_YUVJ420 ? 1 : 0, matrix);
         break;
     }
     case SMR_FRAME_NV12: {
         if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
         SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
-        hipLaunchKernelGGL(k_yuv_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst, 0);
+        hipLaunchKernelGGL(k_yuv_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst, 0, matrix);
         break;
     }
     case SMR_FRAME_PLANAR_YUV420P10: {
         if (!in->planes[1] || !in->planes[2]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing chroma plane");
         hipLaunchKernelGGL(k_yuv_hi_to_rgba<0>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), view_of(in->planes[1]),
-                           view_of(in->planes[2]), dst);
+                           view_of(in->planes[2]), dst, matrix);
         break;
     }
     case SMR_FRAME_P010: {
         if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
         SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
-        hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst);
+        hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst, matrix);
         break;
     }
     case SMR_FRAME_PLANAR_YUV422P10: {  // (k_yuv_hi_to_rgba samples the planes at their own size: (w / 2) x h here)
         if (!in->planes[1] || !in->planes[2]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing chroma plane");
         hipLaunchKernelGGL(k_yuv_hi_to_rgba<0>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), view_of(in->planes[1]),
-                           view_of(in->planes[2]), dst);
+                           view_of(in->planes[2]), dst, matrix);
         break;
     }
     case SMR_FRAME_P210: {
         if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
         SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
-        hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst);
+        hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst, matrix);
         break;
     }
     case SMR_FRAME_V210:
-        hipLaunchKernelGGL(k_yuv422_hi_to_rgba_any<CV422_V210>, grid_px(w, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), dst);
+        hipLaunchKernelGGL(k_yuv422_hi_to_rgba_any<CV422_V210>, grid_px(w, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), dst, matrix);
         break;
     case SMR_FRAME_UYVY422:
     case SMR_FRAME_YUYV422:
         hipLaunchKernelGGL(k_interleaved422_to_rgba, grid_px(w, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), dst,
-                           in->format == SMR_FRAME_UYVY422 ? 0 : 1);
+                           fmt == SMR_FRAME_UYVY422 ? 0 : 1, matrix);
         break;
     case SMR_FRAME_BGRA:
     case SMR_FRAME_ARGB:
         hipLaunchKernelGGL(k_swizzle, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), dst,
-                           in->format == SMR_FRAME_BGRA ? 0 : 1);
+                           fmt == SMR_FRAME_BGRA ? 0 : 1);
         break;
     case SMR_FRAME_RGBA:
         // input_texture/rgba_texture.rs:38-63: straight-alpha texture -> premultiplied node texture
@@ -873,6 +903,7 @@ int smr_rgba_to_frame(smr_ctx *ctx, const smr_surface *node, const smr_frame *ou
     if (node->fmt != SMR_PX_RGBA8 || node->w != out->width || node->h != out->height)
         return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: node must be RGBA8 %ux%u", out->width, out->height);
     if (int rc = smr_validate_frame(ctx, out, "smr_rgba_to_frame")) return rc;
+    if (frame_matrix(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: frame format 0x%x carries a colour matrix: outputs are BT.709, a matrix applies to input frames only", out->format);
     if (frame_format_is_hi_depth(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: frame format %u (10-bit) is input only", out->format);
     StageScope scope(ctx, SMR_STAGE_OUTPUT);
     const int w = (int)out->width, h = (int)out->height;
@@ -927,6 +958,7 @@ int smr_frame_fill_black(smr_ctx *ctx, const smr_frame *out) {
     if (ctx && out)
         if (int rc = smr_validate_frame(ctx, out, "smr_frame_fill_black")) return rc;
     if (!ctx || !out || !out->planes[0]) return SMR_ERR_INVALID;
+    if (frame_matrix(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_fill_black: frame format 0x%x carries a colour matrix: outputs are BT.709, a matrix applies to input frames only", out->format);
     if (frame_format_is_hi_depth(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_fill_black: frame format %u (10-bit) is input only", out->format);
     // RGBColor::BLACK.to_yuv(), smelter-render/src/scene/types.rs:28-41
     const float y = (0.0f * 0.85882354f) + (16.0f / 255.0f);

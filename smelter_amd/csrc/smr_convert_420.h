@@ -93,6 +93,7 @@ struct ConvJob {
     int sx, sy;    // chroma subsampling: 4:2:0 = (1, 1), 4:2:2 = (1, 0), 4:4:4 = (0, 0)
     int rgb12;     // k_yuv420_to_rgba only: dst is an R8 surface of 3 w x h — the node texture as 12-byte groups of four pixels (R x 4, G x 4, B x 4)
     int packed;    // 0 planar / NV12 | 1 UYVY | 2 YUYV: `yp` is the (w / 2) x h plane of U Y0 V Y1 / Y0 U Y1 V groups | 3 BGRA | 4 ARGB: `yp` is the w x h plane, bytes permuted (bgra_to_rgba.wgsl / argb_to_rgba.wgsl:24-28)
+    int matrix;    // smr_color_matrix of the frame (0 = BT.709, what a zeroed job means).  k_yuv420_to_rgba[_tight] do NOT read it: their matrix is a template parameter and the host queues their jobs per matrix
 };
 constexpr int MAX_CONV_JOBS = 16;
 struct ConvBatch {
@@ -282,12 +283,14 @@ struct Cv420StoreNode {
         else g_st_u32x4(J.dst.ptr + cv_mad24((u32)y, J.dst.pitch, 16u * (u32)g), make_uint4(px[0], px[1], px[2], px[3]));
     }
 };
-template <bool RGB12, bool FULL, bool ALLROWS, typename SINK>
+// MATRIX: the frame's smr_color_matrix, a compile-time property of the launch — the instantiations differ in four literals
+template <bool RGB12, bool FULL, bool ALLROWS, typename SINK, int MATRIX = SMR_MATRIX_BT709>
 __device__ __forceinline__ void cv420_rows_to(const ConvJob &J, int g, int P, const u32 yrow[4], const float H[4][2][4], const float *ylut, const SINK &sink) {
     const int h = J.dst.h;
     constexpr bool full = FULL;  // (a template parameter: as a run-time flag it was a scalar branch per pixel)
     constexpr float kc = 0.87843137254f;
     constexpr float rc_hi = 1.0f / kc, rc_lo = (float)(1.0 / (double)kc - (double)rc_hi);
+    constexpr SmrMatrixCoef C = smr_matrix_coef((uint32_t)MATRIX);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int y = 4 * P + r;
@@ -313,9 +316,9 @@ __device__ __forceinline__ void cv420_rows_to(const ConvJob &J, int g, int P, co
                 v = cv_clamp01(__builtin_fmaf(av, rc_hi, av * rc_lo));
             }
             const float um = u - 0.5f, vm = v - 0.5f;
-            const float R = yy + 1.5748f * vm;
-            const float G = yy - 0.1873f * um - 0.4681f * vm;
-            const float B = yy + 1.8556f * um;
+            const float R = yy + C.rv * vm;
+            const float G = yy - C.gu * um - C.gv * vm;
+            const float B = yy + C.bu * um;
             t[0][i] = R * 255.0f + 0.5f;
             t[1][i] = G * 255.0f + 0.5f;
             t[2][i] = B * 255.0f + 0.5f;
@@ -328,9 +331,9 @@ __device__ __forceinline__ void cv420_rows_to(const ConvJob &J, int g, int P, co
         sink(r, y, r4, g4, b4, px);
     }
 }
-template <bool RGB12, bool FULL, bool ALLROWS = false>
+template <bool RGB12, bool FULL, bool ALLROWS = false, int MATRIX = SMR_MATRIX_BT709>
 __device__ __forceinline__ void cv420_rows(const ConvJob &J, int g, int P, const u32 yrow[4], const float H[4][2][4], const float *ylut) {
-    cv420_rows_to<RGB12, FULL, ALLROWS>(J, g, P, yrow, H, ylut, Cv420StoreNode{J, g, RGB12});
+    cv420_rows_to<RGB12, FULL, ALLROWS, Cv420StoreNode, MATRIX>(J, g, P, yrow, H, ylut, Cv420StoreNode{J, g, RGB12});
 }
 
 // One 4 x 4 block: columns 4 g .. 4 g + 3, rows 4 P .. 4 P + 3 of job J (rows past the frame's height are not stored).
@@ -339,7 +342,7 @@ __device__ __forceinline__ void cv420_rows(const ConvJob &J, int g, int P, const
 // dword past the window, 16-byte aligned destination rows.
 // nlut: 256 floats, unorm_of_byte of every byte (the chroma bytes' byte / 255: a table gather instead of a conversion and two multiply-adds)
 // RGB12: the node texture as 12-byte groups (ConvJob::rgb12), else RGBA8 — separate instantiations: each packs its own bytes only
-template <bool NV, bool RGB12, bool FULL, bool TIGHT = false>
+template <bool NV, bool RGB12, bool FULL, bool TIGHT = false, int MATRIX = SMR_MATRIX_BT709>
 __device__ __forceinline__ void cv420_block(const ConvJob &J, int g, int P, const float *ylut, const float *nlut) {
     // every load of the block is in flight before the first store (a row's luma load behind the previous row's store waited for that
     // store and for itself: four memory round trips per block instead of one)
@@ -352,7 +355,7 @@ __device__ __forceinline__ void cv420_block(const ConvJob &J, int g, int P, cons
     float H[4][2][4];  // [window row][plane][luma column]
 #pragma unroll
     for (int j = 0; j < 4; j++) cv420_hrow<NV>(raw[j], W, nlut, H[j]);
-    cv420_rows<RGB12, FULL>(J, g, P, yrow, H, ylut);
+    cv420_rows<RGB12, FULL, false, MATRIX>(J, g, P, yrow, H, ylut);
 }
 
 // A vertical run of blocks: columns 4 g .. 4 g + 3, block rows P0 .. P0 + nb - 1 (those that exist).  The same values as cv420_block on
@@ -364,7 +367,7 @@ __device__ __forceinline__ void cv420_block(const ConvJob &J, int g, int P, cons
 //     while the wave's vector ALU is busy (a one-block thread loads, waits, computes, stores: its waves all wait at the same time);
 //     the run's last block requests nothing (the loop is peeled: inside it the requests are unconditional, so the compiler can count
 //     what is outstanding).
-template <bool NV, bool RGB12, bool FULL, bool TIGHT = false>
+template <bool NV, bool RGB12, bool FULL, bool TIGHT = false, int MATRIX = SMR_MATRIX_BT709>
 __device__ __forceinline__ void cv420_run(const ConvJob &J, int g, int P0, int nb, const float *ylut, const float *nlut, unsigned long long *st = nullptr) {
     const int Pend = min(P0 + nb, (J.dst.h + 3) >> 2);
     if (P0 >= Pend) return;
@@ -389,7 +392,7 @@ __device__ __forceinline__ void cv420_run(const ConvJob &J, int g, int P0, int n
         u32 ynext[4];
         cv420_load_luma(J, g, P + 1, ynext);
         const Cv420Raw<NV> n2 = cv420_load_chroma<NV, TIGHT>(J, W, 2 * P + 3), n3 = cv420_load_chroma<NV, TIGHT>(J, W, 2 * P + 4);
-        cv420_rows<RGB12, FULL, true>(J, g, P, yrow, H, ylut);  // (P + 1 < Pend: not the frame's last block row — all four rows exist)
+        cv420_rows<RGB12, FULL, true, MATRIX>(J, g, P, yrow, H, ylut);  // (P + 1 < Pend: not the frame's last block row — all four rows exist)
         if (P == P0) CV_STAMP(st, 4, "s_nop 0");  // the first block's rows are computed, its stores issued
 #pragma unroll
         for (int c = 0; c < 2; c++)
@@ -400,7 +403,7 @@ __device__ __forceinline__ void cv420_run(const ConvJob &J, int g, int P0, int n
 #pragma unroll
         for (int r = 0; r < 4; r++) yrow[r] = ynext[r];
     }
-    cv420_rows<RGB12, FULL>(J, g, P, yrow, H, ylut);
+    cv420_rows<RGB12, FULL, false, MATRIX>(J, g, P, yrow, H, ylut);
     if (P == P0) CV_STAMP(st, 4, "s_nop 0");
 }
 
@@ -425,6 +428,7 @@ __device__ __forceinline__ SurfView cv420_view_in_registers(const SurfView &v) {
 __device__ __forceinline__ ConvJob cv420_job_in_registers(const ConvJob &j) {
     ConvJob J = j;
     J.yp = cv420_view_in_registers(j.yp); J.up = cv420_view_in_registers(j.up); J.vp = cv420_view_in_registers(j.vp); J.dst = cv420_view_in_registers(j.dst);
+    J.matrix = (int)cv_uniform((u32)j.matrix);  // (read by the 10-bit converters only)
     return J;
 }
 
@@ -432,7 +436,8 @@ __device__ __forceinline__ ConvJob cv420_job_in_registers(const ConvJob &j) {
 // waves cut x's unit sequence (ConvBatch) into equal contiguous shares — total / waves units, the first total % waves waves one more.  A
 // share is a vertical run of blocks inside one (band, column block) cell, or the end of a cell and the start of the next (in the next
 // band or job, too).  ylut: the limited-range luma table; nlut: byte / 255, which is also the full-range luma table.
-template <bool NV, bool TIGHT = false>
+// MATRIX: every job of the launch has this matrix (the host queues k_yuv420_to_rgba's jobs per matrix: smr_frames_to_rgba_batch)
+template <bool NV, bool TIGHT = false, int MATRIX = SMR_MATRIX_BT709>
 __device__ __forceinline__ void cv420_share(const ConvBatch &B, u32 block, u32 wave, u32 grid, u32 lane, const float *ylut, const float *nlut,
                                             unsigned long long *st = nullptr) {
     const u32 x = block & 7u;
@@ -460,11 +465,11 @@ __device__ __forceinline__ void cv420_share(const ConvBatch &B, u32 block, u32 w
             const int P0 = (int)(b * band + r);
             // (uniform branches: a job is one frame; range and node format are template parameters — as run-time flags they cost a scalar branch per pixel)
             if (J.rgb12) {
-                if (J.full) cv420_run<NV, true, true, TIGHT>(J, g, P0, (int)nrun, nlut, nlut, st);
-                else cv420_run<NV, true, false, TIGHT>(J, g, P0, (int)nrun, ylut, nlut, st);
+                if (J.full) cv420_run<NV, true, true, TIGHT, MATRIX>(J, g, P0, (int)nrun, nlut, nlut, st);
+                else cv420_run<NV, true, false, TIGHT, MATRIX>(J, g, P0, (int)nrun, ylut, nlut, st);
             } else {
-                if (J.full) cv420_run<NV, false, true, TIGHT>(J, g, P0, (int)nrun, nlut, nlut, st);
-                else cv420_run<NV, false, false, TIGHT>(J, g, P0, (int)nrun, ylut, nlut, st);
+                if (J.full) cv420_run<NV, false, true, TIGHT, MATRIX>(J, g, P0, (int)nrun, nlut, nlut, st);
+                else cv420_run<NV, false, false, TIGHT, MATRIX>(J, g, P0, (int)nrun, ylut, nlut, st);
             }
         }
         st = nullptr;  // (timing builds: only the share's first run is stamped phase by phase)

@@ -6,16 +6,17 @@
 
 #ifdef __HIPCC__
 
-// planar_yuv_to_rgba.wgsl:45-57: limited->full range (unless J), BT.709 matrix, clamp, unorm8 store.
-__device__ __forceinline__ u32 yuv_to_rgb_px(float y, float u, float v, bool full) {
+// planar_yuv_to_rgba.wgsl:45-57: limited->full range (unless J), the matrix (BT.709: the reference's; the frame's own where it carries one —
+// smr_matrix_coef, smr_frame_formats.h: the same statements with other constants), clamp, unorm8 store.
+__device__ __forceinline__ u32 yuv_to_rgb_px(float y, float u, float v, bool full, const SmrMatrixCoef C = smr_matrix_coef(SMR_MATRIX_BT709)) {
     if (!full) {
         y = clampf((y - (16.0f / 255.0f)) / 0.85882352941f, 0.0f, 1.0f);
         u = clampf((u - (16.0f / 255.0f)) / 0.87843137254f, 0.0f, 1.0f);
         v = clampf((v - (16.0f / 255.0f)) / 0.87843137254f, 0.0f, 1.0f);
     }
-    float r = y + 1.5748f * (v - 0.5f);
-    float g = y - 0.1873f * (u - 0.5f) - 0.4681f * (v - 0.5f);
-    float b = y + 1.8556f * (u - 0.5f);
+    float r = y + C.rv * (v - 0.5f);
+    float g = y - C.gu * (u - 0.5f) - C.gv * (v - 0.5f);
+    float b = y + C.bu * (u - 0.5f);
     return unorm8(r) | (unorm8(g) << 8) | (unorm8(b) << 16) | 0xff000000u;
 }
 
@@ -24,7 +25,7 @@ __device__ __forceinline__ u32 yuv_to_rgb_px(float y, float u, float v, bool ful
 // per divisor and on every byte, and on the GPU against k_yuv_to_rgba frame by frame (tests/test_gpu_parity.py).
 // The clamps are one v_med3_f32 each (operands are finite; a -0 where clampf gives +0 is absorbed by the sums that follow).
 #ifndef SMR_EMU  // (k_yuv_to_rgba_batch only: not part of the kernels the lane emulator compiles)
-__device__ __forceinline__ u32 yuv_to_rgb_px_cr(float y, float u, float v, bool full) {
+__device__ __forceinline__ u32 yuv_to_rgb_px_cr(float y, float u, float v, bool full, const SmrMatrixCoef C = smr_matrix_coef(SMR_MATRIX_BT709)) {
     if (!full) {
         constexpr float ky = 0.85882352941f, kc = 0.87843137254f;
         const float ry = 1.0f / ky, rc = 1.0f / kc;
@@ -34,9 +35,9 @@ __device__ __forceinline__ u32 yuv_to_rgb_px_cr(float y, float u, float v, bool 
         u = __builtin_amdgcn_fmed3f(__builtin_fmaf(__builtin_fmaf(-qu, kc, au), rc, qu), 0.0f, 1.0f);
         v = __builtin_amdgcn_fmed3f(__builtin_fmaf(__builtin_fmaf(-qv, kc, av), rc, qv), 0.0f, 1.0f);
     }
-    const float r = y + 1.5748f * (v - 0.5f);
-    const float g = y - 0.1873f * (u - 0.5f) - 0.4681f * (v - 0.5f);
-    const float b = y + 1.8556f * (u - 0.5f);
+    const float r = y + C.rv * (v - 0.5f);
+    const float g = y - C.gu * (u - 0.5f) - C.gv * (v - 0.5f);
+    const float b = y + C.bu * (u - 0.5f);
     const u32 r8 = (u32)(int)(__builtin_amdgcn_fmed3f(r, 0.0f, 1.0f) * 255.0f + 0.5f);
     const u32 g8 = (u32)(int)(__builtin_amdgcn_fmed3f(g, 0.0f, 1.0f) * 255.0f + 0.5f);
     const u32 b8 = (u32)(int)(__builtin_amdgcn_fmed3f(b, 0.0f, 1.0f) * 255.0f + 0.5f);

@@ -176,6 +176,7 @@ __device__ __forceinline__ void cvhi_rows(const ConvJob &J, int g, int P, const 
     const int h = J.dst.h;
     constexpr float kc = 0.87843137254f;
     constexpr float rc_hi = 1.0f / kc, rc_lo = (float)(1.0 / (double)kc - (double)rc_hi);
+    const SmrMatrixCoef C = smr_matrix_coef((u32)J.matrix);  // (uniform: the job's matrix sits in a scalar register, cv420_job_in_registers; not on the benchmark's path, so no instantiation per matrix)
     const Cv420StoreNode sink{J, g, RGB12};
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -196,9 +197,9 @@ __device__ __forceinline__ void cvhi_rows(const ConvJob &J, int g, int P, const 
             u = cv_clamp01(__builtin_fmaf(au, rc_hi, au * rc_lo));
             v = cv_clamp01(__builtin_fmaf(av, rc_hi, av * rc_lo));
             const float um = u - 0.5f, vm = v - 0.5f;
-            const float R = yy + 1.5748f * vm;
-            const float G = yy - 0.1873f * um - 0.4681f * vm;
-            const float B = yy + 1.8556f * um;
+            const float R = yy + C.rv * vm;
+            const float G = yy - C.gu * um - C.gv * vm;
+            const float B = yy + C.bu * um;
             t[0][i] = R * 255.0f + 0.5f;
             t[1][i] = G * 255.0f + 0.5f;
             t[2][i] = B * 255.0f + 0.5f;

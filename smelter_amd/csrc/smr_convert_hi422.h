@@ -73,6 +73,7 @@ __device__ __forceinline__ void cv422_rows(const ConvJob &J, int g, int P, const
     const int h = J.dst.h;
     constexpr float kc = 0.87843137254f;
     constexpr float rc_hi = 1.0f / kc, rc_lo = (float)(1.0 / (double)kc - (double)rc_hi);
+    const SmrMatrixCoef C = smr_matrix_coef((u32)J.matrix);  // (uniform, as in cvhi_rows)
     const Cv420StoreNode sink{J, g, RGB12};
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -93,9 +94,9 @@ __device__ __forceinline__ void cv422_rows(const ConvJob &J, int g, int P, const
             u = cv_clamp01(__builtin_fmaf(au, rc_hi, au * rc_lo));
             v = cv_clamp01(__builtin_fmaf(av, rc_hi, av * rc_lo));
             const float um = u - 0.5f, vm = v - 0.5f;
-            const float R = yy + 1.5748f * vm;
-            const float G = yy - 0.1873f * um - 0.4681f * vm;
-            const float B = yy + 1.8556f * um;
+            const float R = yy + C.rv * vm;
+            const float G = yy - C.gu * um - C.gv * vm;
+            const float B = yy + C.bu * um;
             t[0][i] = R * 255.0f + 0.5f;
             t[1][i] = G * 255.0f + 0.5f;
             t[2][i] = B * 255.0f + 0.5f;
@@ -159,6 +160,7 @@ __device__ __forceinline__ void cv210_rows(const ConvJob &J, int g, u32 m, int P
     const int h = J.dst.h;
     constexpr float kc = 0.87843137254f;
     constexpr float rc_hi = 1.0f / kc, rc_lo = (float)(1.0 / (double)kc - (double)rc_hi);
+    const SmrMatrixCoef C = smr_matrix_coef((u32)J.matrix);  // (uniform, as in cvhi_rows)
     const Cv420StoreNode sink{J, g, RGB12};
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -179,7 +181,7 @@ __device__ __forceinline__ void cv210_rows(const ConvJob &J, int g, u32 m, int P
             const float u = cv_clamp01(__builtin_fmaf(au, rc_hi, au * rc_lo));
             const float v = cv_clamp01(__builtin_fmaf(av, rc_hi, av * rc_lo));
             const float um = u - 0.5f, vm = v - 0.5f;
-            const float rv = 1.5748f * vm, gu = 0.1873f * um, gv = 0.4681f * vm, bu = 1.8556f * um;  // (the matrix products: per pair)
+            const float rv = C.rv * vm, gu = C.gu * um, gv = C.gv * vm, bu = C.bu * um;  // (the matrix products: per pair)
 #pragma unroll
             for (int i = 2 * p; i < 2 * p + 2; i++) {
                 const float yy = ylut[yc[i]];

@@ -461,9 +461,11 @@ int smr_surface_clear(smr_ctx *ctx, smr_surface *s) {
 // ------------------------------------------------------------------------------ frames
 // plane geometry per FrameData variant (wgpu/texture/planar_yuv.rs:65-84, nv12.rs,
 // interleaved_yuv422.rs, bgra_linear.rs, argb_linear.rs)
+// (geometry comes from the BASE format: the colour matrix in bits 8 - 11 changes no plane; a value with a bad tag has no geometry)
 static int plane_geometry(u32 format, u32 w, u32 h, u32 pw[3], u32 ph[3], u32 pf[3]) {
     for (int i = 0; i < 3; i++) pw[i] = ph[i] = 0, pf[i] = SMR_PX_R8;
-    switch (format) {
+    if (frame_format_tag_error(format)) return 0;
+    switch (frame_base_format(format)) {
     case SMR_FRAME_PLANAR_YUV420:
     case SMR_FRAME_PLANAR_YUVJ420:
         pw[0] = w; ph[0] = h; pw[1] = pw[2] = w / 2; ph[1] = ph[2] = h / 2; return 3;
@@ -499,6 +501,7 @@ static int plane_geometry(u32 format, u32 w, u32 h, u32 pw[3], u32 ph[3], u32 pf
 int smr_validate_frame(smr_ctx *ctx, const smr_frame *f, const char *what) {
     if (!f) return smr_fail(ctx, SMR_ERR_INVALID, "%s: null frame", what);
     u32 pw[3], ph[3], pf[3];
+    if (const char *why = frame_format_tag_error(f->format)) return smr_fail(ctx, SMR_ERR_INVALID, "%s: frame format 0x%x: %s", what, f->format, why);
     const int n = plane_geometry(f->format, f->width, f->height, pw, ph, pf);
     if (n == 0) return smr_fail(ctx, SMR_ERR_INVALID, "%s: unknown frame format %u", what, f->format);
     if (f->width == 0 || f->height == 0) return smr_fail(ctx, SMR_ERR_INVALID, "%s: empty frame", what);
@@ -518,6 +521,7 @@ int smr_frame_create(smr_ctx *ctx, uint32_t format, uint32_t w, uint32_t h, smr_
     if (!ctx || !out) return SMR_ERR_INVALID;
     memset(out, 0, sizeof(*out));
     u32 pw[3], ph[3], pf[3];
+    if (const char *why = frame_format_tag_error(format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_create: frame format 0x%x: %s", format, why);
     int n = plane_geometry(format, w, h, pw, ph, pf);
     if (n == 0) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_create: unknown frame format %u", format);
     out->format = format;

@@ -14,6 +14,7 @@ from . import _ffi
 from ._ffi import (FRAME_ARGB, FRAME_BGRA, FRAME_NV12, FRAME_P010, FRAME_P210, FRAME_PLANAR_YUV420, FRAME_PLANAR_YUV420P10, FRAME_PLANAR_YUV422,
                    FRAME_PLANAR_YUV422P10, FRAME_V210, FRAME_PLANAR_YUV444, FRAME_PLANAR_YUVJ420, FRAME_RGBA, FRAME_UYVY422, FRAME_YUYV422, MODE_CPU_OPTIMIZED,
                    MODE_GPU_OPTIMIZED, PX_R8, PX_R16, PX_RG8, PX_RG16, PX_RGBA8, PX_RGBA16F)
+from ._ffi import MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020_NCL, frame_base_format, frame_format, frame_matrix  # noqa: F401
 from ._ffi import (SHADER_CIRCLE_LAYOUT, SHADER_COLOR_BY_TEXTURE_COUNT, SHADER_FADE_TO_BALL, SHADER_GAUSSIAN_BLUR,  # noqa: F401
                    SHADER_GRADIENT, SHADER_LAYOUT_PLANES, SHADER_MAX_SOURCES, SHADER_RED_BORDER, SHADER_SILLY)
 
@@ -83,7 +84,7 @@ class DeviceFrame:
         ctx._check(ctx.lib.smr_frame_create(ctx.handle, fmt, w, h, C.byref(self.c)))
 
     def plane_shapes(self):
-        w, h, f = self.w, self.h, self.fmt
+        w, h, f = self.w, self.h, frame_base_format(self.fmt)  # (the colour matrix in bits 8 - 11 changes no plane)
         if f in (FRAME_PLANAR_YUV420, FRAME_PLANAR_YUVJ420, FRAME_PLANAR_YUV420P10):
             return [(h, w), (h // 2, w // 2), (h // 2, w // 2)]
         if f in (FRAME_PLANAR_YUV422, FRAME_PLANAR_YUV422P10):
@@ -102,9 +103,10 @@ class DeviceFrame:
 
     def plane_dtype(self):
         """The element type of every plane: 16-bit words for the 10-bit formats (v210: dwords of three codes), bytes otherwise."""
-        if self.fmt == FRAME_V210:
+        f = frame_base_format(self.fmt)
+        if f == FRAME_V210:
             return np.uint32
-        return np.uint16 if self.fmt in (FRAME_P010, FRAME_PLANAR_YUV420P10, FRAME_P210, FRAME_PLANAR_YUV422P10) else np.uint8
+        return np.uint16 if f in (FRAME_P010, FRAME_PLANAR_YUV420P10, FRAME_P210, FRAME_PLANAR_YUV422P10) else np.uint8
 
     def upload(self, planes: Sequence[np.ndarray]) -> "DeviceFrame":
         shapes = self.plane_shapes()
