@@ -608,7 +608,7 @@ extern "C" int smr_render_layouts(smr_ctx *ctx, const smr_layout *layouts, uint3
         if (n_banded > b_tiles * (u32)B_AREA_BANDS) n_banded = b_tiles * (u32)B_AREA_BANDS;
         if (ctx->debug_ingest)
             fprintf(stderr, "k_compose_output: %u tiles, %u bands on the list (%s; predicted tiles %u, last read back %u)\n", b_tiles, n_banded, cm->count_known ? "known" : "predicted", n_first, *cm->h_count);
-        dim3 grid(n_banded + (b_tiles + B_COPY_TILES - 1) / B_COPY_TILES, 1, 1);
+        dim3 grid(n_banded + (b_tiles + B_COPY_RUN - 1) / B_COPY_RUN, 1, 1);  // (a copy workgroup walks a run of B_COPY_RUN tiles)
         const TileList *full = (const TileList *)cm->d_list;
         const TileClass *tc = (const TileClass *)cm->d_class;
         const int flags = (ctx->srgb() ? 1 : 0) | ((ctx->ablate >> 8) << 8);

@@ -20,6 +20,14 @@
 
 namespace {
 
+// A per-lane value the compiler can neither prove loop-invariant nor compute ahead of this point: what is derived from it (a block's
+// position, its store addresses) is formed where it is used instead of being held in registers from the top of the loop or the function.
+#ifdef SMR_EMU
+#define B_KEEP_IN_LOOP(x) do { } while (0)
+#else
+#define B_KEEP_IN_LOOP(x) asm volatile("" : "+v"(x))
+#endif
+
 // row * pitch + offset as one full-rate v_mad_u32_u24 (rows and pitches are below 2^24, a surface below 4 GiB); the 64-bit form is a
 // quarter-rate 32 x 32 multiply per address
 __device__ __forceinline__ u32 b_off(int row, u32 pitch, int col_bytes) { return (u32)__umul24((u32)row, pitch) + (u32)col_bytes; }
@@ -363,8 +371,71 @@ __device__ __forceinline__ u32 compose_px(u32 a, const DevLayout &L, const DevMa
     return blend_store(a, frag, srgb, dec, thr);
 }
 
+// The cold half of store_yuv_block's conversion: a lane with a guard flag among its block's twelve plane values (2.4 values in 10 000 raise
+// one) computes those values again with the reference sequence itself (unorm_of_byte, yuv_byte, the ((a + b) + (c + d)) / 4 mean of
+// smr_convert_dev.h) and replaces their bytes in the packed results.  Everything the sequence needs — byte / 255 of all 24 channel bytes —
+// is computed here, behind the block's ONE branch: with a branch per value (yuv_luma_byte / yuv_chroma_bytes) the compiler hoisted these
+// operands, common to all twelve branches, above them, onto every pixel's path.  It starts again from the block's bytes (opaque copies:
+// nothing of the fast path — the bytes as floats, the flags — is kept alive for it), constant indices only (no scratch).
+__device__ __forceinline__ void yuv_block_repair(const u32 (&acc)[8], u32 &yrow0, u32 &yrow1, u32 &u2, u32 &v2) {
+    u32 px[8];
+    float r[8], g[8], b[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        px[k] = acc[k];
+        B_KEEP_IN_LOOP(px[k]);
+        r[k] = unorm_of_byte(px[k] & 0xffu);
+        g[k] = unorm_of_byte((px[k] >> 8) & 0xffu);
+        b[k] = unorm_of_byte((px[k] >> 16) & 0xffu);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        bool f;
+        (void)yuvfast::convert<0>((float)(px[k] & 0xffu), (float)((px[k] >> 8) & 0xffu), (float)((px[k] >> 16) & 0xffu), &f);
+        const u32 exact = yuv_byte(r[k], g[k], b[k], 0), sh = 8u * (u32)(k & 3);
+        u32 &row = k < 4 ? yrow0 : yrow1;
+        row = f ? ((row & ~(0xffu << sh)) | (exact << sh)) : row;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int a = 2 * j, c = 4 + 2 * j;
+        float sum[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++)
+            sum[ch] = ((float)((px[a] >> (8 * ch)) & 0xffu) + (float)((px[a + 1] >> (8 * ch)) & 0xffu)) +
+                      ((float)((px[c] >> (8 * ch)) & 0xffu) + (float)((px[c + 1] >> (8 * ch)) & 0xffu));
+        bool f1, f2;
+        (void)yuvfast::convert<1>(sum[0], sum[1], sum[2], &f1);
+        (void)yuvfast::convert<2>(sum[0], sum[1], sum[2], &f2);
+        const float mr = ((r[a] + r[a + 1]) + (r[c] + r[c + 1])) * 0.25f, mg = ((g[a] + g[a + 1]) + (g[c] + g[c + 1])) * 0.25f,
+                    mb = ((b[a] + b[a + 1]) + (b[c] + b[c + 1])) * 0.25f;
+        const u32 eu = yuv_byte(mr, mg, mb, 1), ev = yuv_byte(mr, mg, mb, 2), sh = 8u * (u32)j;
+        u2 = f1 ? ((u2 & ~(0xffu << sh)) | (eu << sh)) : u2;
+        v2 = f2 ? ((v2 & ~(0xffu << sh)) | (ev << sh)) : v2;
+    }
+}
+
+// Whether a tile's blocks may be stored by lane pairs (store_yuv_block's `pair`, decided once per tile, wave-uniformly): the tile lies wholly
+// inside the output — every lane of every wave holds a whole 4 x 2 block — and the planes' bases and pitches keep a pair's 8 bytes of Y'
+// and 4 bytes of U / V naturally aligned (the library's own planes always; a wrapped frame with tight rows of odd width does not).
 template <int NV>
-__device__ __forceinline__ void store_yuv_block(const u32 (&acc)[8], int px0, int py0, int W, const SurfView &yp, const SurfView &up, const SurfView &vp) {
+__device__ __forceinline__ bool planes_pair_aligned(const SurfView &yp, const SurfView &up, const SurfView &vp) {
+#if defined(SMR_EMU) && !defined(SMR_EMU_WAVE_EXCHANGE)
+    return false;  // (a harness of the lane emulator that sets up no per-wave exchange — tests/emu/emu_compose.cpp: the per-lane stores everywhere)
+#else
+    if (NV == 2) return false;
+    bool ok = ((((uintptr_t)yp.ptr) | yp.pitch) & 7u) == 0;
+    if (NV == 0) ok = ok && ((((uintptr_t)up.ptr) | up.pitch | ((uintptr_t)vp.ptr) | vp.pitch) & 3u) == 0;
+    return ok;
+#endif
+}
+
+// `pair` (wave-uniform; only where every lane of the wave makes this call): lanes l and l ^ 1 — horizontally adjacent blocks — exchange
+// halves, so that the even lane stores 8 bytes of Y' row 0 and the odd lane 8 bytes of row 1, and for planar output the even lane 4 bytes of
+// U and the odd lane 4 bytes of V: two store instructions per lane instead of four, the same bytes.
+template <int NV>
+__device__ __forceinline__ void store_yuv_block(const u32 (&acc)[8], int px0, int py0, int W, const SurfView &yp, const SurfView &up, const SurfView &vp,
+                                                bool pair = false) {
     // (W is even: the last block of a row holds four or two pixels)
     const bool half = px0 + 3 >= W;
     if (NV == 2) {  // an RGBA8 node texture (LayoutNode::render into a NodeTexture): the composited bytes as they are
@@ -379,8 +450,8 @@ __device__ __forceinline__ void store_yuv_block(const u32 (&acc)[8], int px0, in
         return;
     }
     // RGBA -> Y'CbCr on the raw (gamma-encoded) bytes: rgba_to_yuv.wgsl:26-54 / rgba_to_nv12.wgsl:24-52 — the bytes yuv_component() /
-    // unorm8() compute, through the fast path of smr_yuv_fast.h: three FMAs per value on the bytes as floats, the reference sequence itself
-    // (unorm_of_byte, yuv_byte) only where the guard flag asks for it (smr_convert_dev.h: yuv_luma_byte, yuv_chroma_bytes)
+    // unorm8() compute, through the fast path of smr_yuv_fast.h: three FMAs per value on the bytes as floats.  The twelve guard flags of the
+    // block are gathered into one condition per lane and ONE branch leads to the reference sequence (yuv_block_repair).
     float cr[8], cg[8], cb[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
@@ -388,11 +459,47 @@ __device__ __forceinline__ void store_yuv_block(const u32 (&acc)[8], int px0, in
         cg[k] = (float)((acc[k] >> 8) & 0xffu);
         cb[k] = (float)((acc[k] >> 16) & 0xffu);
     }
-    u32 yrow0 = 0, yrow1 = 0;
+    u32 yrow0 = 0, yrow1 = 0, u2 = 0, v2 = 0;  // Y' of the block's two rows, its two U and its two V bytes
+    bool flagged = false;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        yrow0 |= yuv_luma_byte(acc[k], cr[k], cg[k], cb[k]) << (8 * k);
-        yrow1 |= yuv_luma_byte(acc[4 + k], cr[4 + k], cg[4 + k], cb[4 + k]) << (8 * k);
+        bool f0, f1;
+        yrow0 |= yuvfast::convert<0>(cr[k], cg[k], cb[k], &f0) << (8 * k);
+        yrow1 |= yuvfast::convert<0>(cr[4 + k], cg[4 + k], cb[4 + k], &f1) << (8 * k);
+        flagged |= f0 | f1;
+    }
+    // chroma: the bilinear tap at the chroma texel centre = weights (1/2, 1/2) x (1/2, 1/2):
+    //     (a * .5 + b * .5) * .5 + (c * .5 + d * .5) * .5  ==  ((a + b) + (c + d)) * .25   bit for bit
+    // (a power of two scales exactly and commutes with rounding — the operands are 0 or >= 1/255, nowhere near the subnormals);
+    // the fast path takes the block's byte sums (exact in f32)
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int a = 2 * j, b = 2 * j + 1, c = 4 + 2 * j, d = 4 + 2 * j + 1;
+        const float sr = (cr[a] + cr[b]) + (cr[c] + cr[d]), sg = (cg[a] + cg[b]) + (cg[c] + cg[d]), sb = (cb[a] + cb[b]) + (cb[c] + cb[d]);
+        bool f1, f2;
+        u2 |= yuvfast::convert<1>(sr, sg, sb, &f1) << (8 * j);
+        v2 |= yuvfast::convert<2>(sr, sg, sb, &f2) << (8 * j);
+        flagged |= f1 | f2;
+    }
+    if (flagged) {
+        YUV_SLOW_PATH_STAYS_A_BRANCH();
+        yuv_block_repair(acc, yrow0, yrow1, u2, v2);
+    }
+    const u32 uv4 = (u2 & 0xffu) | ((v2 & 0xffu) << 8) | ((u2 & 0xff00u) << 8) | ((v2 & 0xff00u) << 16);  // NV12: U V U V
+    const int cx = px0 >> 1, cy = py0 >> 1;
+    if (pair) {  // (an interior tile: no half block, px0 = 4 * lane within the row)
+        const bool odd = (px0 & 4) != 0;
+        // the even lane gets its right neighbour's row 0, the odd lane its left neighbour's row 1
+        const u32 ny = (u32)dev_mov_dpp_quad_swap((int)(odd ? yrow0 : yrow1));
+        g_st_u32x2(yp.ptr + b_off(py0 + (odd ? 1 : 0), yp.pitch, px0 & ~7), odd ? ny : yrow0, odd ? yrow1 : ny);
+        if (NV == 0) {
+            const u32 nc = (u32)dev_mov_dpp_quad_swap((int)(odd ? u2 : v2));  // even: the neighbour's U pair, odd: the neighbour's V pair
+            u8 *o = odd ? vp.ptr + b_off(cy, vp.pitch, cx & ~3) : up.ptr + b_off(cy, up.pitch, cx);
+            g_st_u32(o, odd ? (nc | (v2 << 16)) : (u2 | (nc << 16)));
+        } else {
+            *(u32 *)(up.ptr + b_off(cy, up.pitch, cx * 2)) = uv4;
+        }
+        return;
     }
     if (half) {
         *(u16 *)(yp.ptr + b_off(py0, yp.pitch, px0)) = (u16)yrow0;
@@ -401,32 +508,18 @@ __device__ __forceinline__ void store_yuv_block(const u32 (&acc)[8], int px0, in
         *(u32 *)(yp.ptr + b_off(py0, yp.pitch, px0)) = yrow0;
         *(u32 *)(yp.ptr + b_off(py0 + 1, yp.pitch, px0)) = yrow1;
     }
-    // chroma: the bilinear tap at the chroma texel centre = weights (1/2, 1/2) x (1/2, 1/2):
-    //     (a * .5 + b * .5) * .5 + (c * .5 + d * .5) * .5  ==  ((a + b) + (c + d)) * .25   bit for bit
-    // (a power of two scales exactly and commutes with rounding — the operands are 0 or >= 1/255, nowhere near the subnormals);
-    // the fast path takes the block's byte sums (exact in f32)
-    u32 uv[2][2];
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const int a = 2 * j, b = 2 * j + 1, c = 4 + 2 * j, d = 4 + 2 * j + 1;
-        const u32 q = yuv_chroma_bytes(acc[a], acc[b], acc[c], acc[d], (cr[a] + cr[b]) + (cr[c] + cr[d]), (cg[a] + cg[b]) + (cg[c] + cg[d]),
-                                       (cb[a] + cb[b]) + (cb[c] + cb[d]));
-        uv[j][0] = q & 0xffu;
-        uv[j][1] = q >> 8;
-    }
-    const int cx = px0 >> 1, cy = py0 >> 1;
     if (NV == 0) {
         if (half) {
-            up.ptr[b_off(cy, up.pitch, cx)] = (u8)uv[0][0];
-            vp.ptr[b_off(cy, vp.pitch, cx)] = (u8)uv[0][1];
+            up.ptr[b_off(cy, up.pitch, cx)] = (u8)u2;
+            vp.ptr[b_off(cy, vp.pitch, cx)] = (u8)v2;
         } else {
-            *(u16 *)(up.ptr + b_off(cy, up.pitch, cx)) = (u16)(uv[0][0] | (uv[1][0] << 8));
-            *(u16 *)(vp.ptr + b_off(cy, vp.pitch, cx)) = (u16)(uv[0][1] | (uv[1][1] << 8));
+            *(u16 *)(up.ptr + b_off(cy, up.pitch, cx)) = (u16)u2;
+            *(u16 *)(vp.ptr + b_off(cy, vp.pitch, cx)) = (u16)v2;
         }
     } else if (half) {
-        *(u16 *)(up.ptr + b_off(cy, up.pitch, cx * 2)) = (u16)(uv[0][0] | (uv[0][1] << 8));
+        *(u16 *)(up.ptr + b_off(cy, up.pitch, cx * 2)) = (u16)uv4;
     } else {
-        *(u32 *)(up.ptr + b_off(cy, up.pitch, cx * 2)) = uv[0][0] | (uv[0][1] << 8) | (uv[1][0] << 16) | (uv[1][1] << 24);
+        *(u32 *)(up.ptr + b_off(cy, up.pitch, cx * 2)) = uv4;
     }
 }
 
@@ -488,7 +581,9 @@ __device__ __forceinline__ void compose_full(const TileFull *__restrict__ pre, i
     // dependent scalar-memory round trip per field per layer per wave
     __shared__ __attribute__((aligned(16))) DevLayout s_lay[B_MAX_LAYOUTS];
     __shared__ __attribute__((aligned(16))) DevMask s_mask[B_MAX_MASKS];
-    const int tid = threadIdx.x;
+    int tid = threadIdx.x;
+    B_KEEP_IN_LOOP(tid);  // (called band after band: the copy addresses below are formed per call, not held in registers across the calls)
+    tid &= 255;           // (what the compiler knew about threadIdx.x)
     u32 acc[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // this thread's 4x2 output block, [row][col]: acc[r * 4 + c]
     const int tile_y = tile / tiles_x;
     const int tx0 = (tile - tile_y * tiles_x) * B_TILE_W, ty0 = tile_y * B_TILE_H + band;
@@ -670,23 +765,55 @@ __device__ __forceinline__ void compose_full(const TileFull *__restrict__ pre, i
     }
     __syncthreads();
     if (!no_block) {
-        const int lx0 = px0 - tx0, ly0 = py0 - ty0;
+        int ltid = tid;
+        B_KEEP_IN_LOOP(ltid);  // (the block's position again, here: its store addresses are not carried through the three steps above)
+        const int lx0 = 4 * (ltid & 31), ly0 = 2 * (ltid >> 5), px0 = tx0 + lx0, py0 = ty0 + ly0;
         const uint4 t0 = *(const uint4 *)&s_px[ly0 * B_TILE_W + lx0], t1 = *(const uint4 *)&s_px[(ly0 + 1) * B_TILE_W + lx0];
         acc[0] = t0.x; acc[1] = t0.y; acc[2] = t0.z; acc[3] = t0.w;
         acc[4] = t1.x; acc[5] = t1.y; acc[6] = t1.z; acc[7] = t1.w;
-        store_yuv_block<NV>(acc, px0, py0, W, yp, up, vp);
+        // (an interior tile's band of four or eight rows: whole waves hold blocks, the others skipped this branch together)
+        const bool pair = tx0 + B_TILE_W <= W && tile_y * B_TILE_H + B_TILE_H <= H && (rh & 3) == 0 && planes_pair_aligned<NV>(yp, up, vp);
+        store_yuv_block<NV>(acc, px0, py0, W, yp, up, vp, pair);
     }
 }
 
-// Copy tiles per workgroup of the kernel's second part (their records, then all their texels, are fetched back to back).
-// Measured on configs[2]: 1 -> 29 us, 4 -> 37 us for the whole kernel — the conversion arithmetic of four tiles in one workgroup
-// outweighs the launches saved.  Round 4, same kernel three rounds later (tools/r04_run16.sh, -DSMR_COPY_TILES=2): 22.5 -> 29.9 us on configs[2],
-// 45.3 -> 53.1 us on configs[4]: still one.
-#ifndef SMR_COPY_TILES
-#define SMR_COPY_TILES 1
+// Copy tiles per workgroup: B_COPY_TILES is the number of tiles a workgroup holds AT ONCE (one: measured with two and four, whose texels were
+// all live and converted back to back — 29 -> 37 us in round 3, 22.5 -> 29.9 us in round 4); the lane emulator's harness sizes its grid by it.
+// B_COPY_RUN is the number of consecutive row-major tiles the product launch gives a copy workgroup, which walks them ONE AFTER THE OTHER
+// with the next tile's texels on their way while it converts this one's: a wave's start-up (kernel arguments, the division by tiles_x, the
+// class record, and only then the texel request) is paid once per run instead of once per tile, and the conversion overlaps the trip.
+// Even values: two adjacent tiles' 64-byte chroma rows complete 128-byte lines from one CU.  The grid stays several times what is resident
+// (configs[2]: 4 050 tiles -> 2 025 workgroups against 256 CUs x 6): the hardware still balances the workgroups.
+constexpr int B_COPY_TILES = 1;
+#ifndef SMR_COPY_RUN
+#define SMR_COPY_RUN 2
 #endif
-constexpr int B_COPY_TILES = SMR_COPY_TILES;
-static_assert(B_COPY_TILES == 1 || B_COPY_TILES == 2, "one or two tiles per workgroup");
+constexpr int B_COPY_RUN = SMR_COPY_RUN;
+static_assert(B_COPY_RUN >= 1 && B_COPY_RUN <= 4, "a short run: the grid stays larger than what is resident");
+
+// The eight texels of this lane's 4 x 2 block of a copy tile (clear / colour: the fill value), requested and not waited for.
+// `aligned` (uniform): the tile's texel rows can be read 16 bytes at a time; a lane with nothing to read reads the tables instead — no
+// branch between the loads.  A 1:1 blit of an opaque texture: decode -> encode is the identity.
+__device__ __forceinline__ void copy_tile_texels(const TileClass &c, bool on, int cols, int bx, int by, const float *__restrict__ tables, u32 (&t)[8]) {
+    const u32 fill = c.kind == TC_COLOUR ? c.pitch_or_px : 0u;
+#pragma unroll
+    for (int q = 0; q < 8; q++) t[q] = fill;
+    if (c.kind != TC_TEXTURE) return;  // (uniform)
+    // (cols = the output's columns from the tile's first on; a width of 2 mod 4 makes the row's last block two pixels wide)
+    const bool aligned = ((((uintptr_t)c.base) | c.pitch_or_px) & 15) == 0 && !((cols & 3) != 0 && cols < B_TILE_W);
+    if (aligned) {
+        const u8 *r0 = on ? c.base + b_off(by, c.pitch_or_px, bx * 4) : (const u8 *)tables;
+        const u8 *r1 = on ? r0 + c.pitch_or_px : (const u8 *)tables;
+        const uint4 ra = g_ld_u32x4(r0), rb = g_ld_u32x4(r1);  // (global loads: a base from a record in memory is a generic pointer to the compiler — smr_internal.h)
+        t[0] = ra.x; t[1] = ra.y; t[2] = ra.z; t[3] = ra.w;
+        t[4] = rb.x; t[5] = rb.y; t[6] = rb.z; t[7] = rb.w;
+    } else if (on) {
+        const u8 *r0 = c.base + b_off(by, c.pitch_or_px, bx * 4), *r1 = r0 + c.pitch_or_px;
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (bx + q < cols) { t[q] = g_ld_u32(r0 + 4 * q); t[4 + q] = g_ld_u32(r1 + 4 * q); }
+    }
+}
 
 template <int NV, bool BIG>
 __global__ __launch_bounds__(256, B_MIN_WAVES) void k_compose_output(SurfView yp, SurfView up, SurfView vp, int W, int H,
@@ -701,145 +828,138 @@ __global__ __launch_bounds__(256, B_MIN_WAVES) void k_compose_output(SurfView yp
     __shared__ __attribute__((aligned(16))) float s_tab[SMR_TABLE_FLOATS];  // decode / encode tables (whoever needs them loads them)
     // The first `n_banded` workgroups take the bands of the tiles that need compositing, an entry of the TileList each (the host sized the
     // grid from the list's length when it knows it, from its own prediction otherwise) — they are latency-bound and would be the tail of
-    // the kernel.  Every other workgroup takes B_COPY_TILES consecutive tiles of the row-major order.
-    // (the compositing path is most of the kernel's code: it is instantiated once, at the end, and both ways into it — a band of a
+    // the kernel.  Every other workgroup g = blockIdx.x - n_banded takes the run of consecutive row-major tiles [g T, min((g + 1) T, tiles)),
+    // T = ceil(tiles / (gridDim.x - n_banded)): the product launch sizes the grid for T = B_COPY_RUN, a grid of n_banded + tiles gives T = 1.
+    // (the compositing path is most of the kernel's code: it is instantiated once, inside the walk, and both ways into it — a band of a
     //  listed tile; a tile the list had no room for — only choose its arguments)
     const int rest = (int)blockIdx.x - n_banded;
-    const TileFull *full_entry = nullptr, *full_entry2 = nullptr;
-    int full_entries = 1, full_entries2 = 1;
+    int t_begin = 0, t_end = 0;  // the run
+    bool later = false, left_out = false;  // (uniform) tiles of the run that are sampled or select tiles / that are composited here: after the walk
     if (rest < 0) {
         if (blockIdx.x >= full->count[counter]) return;
-        full_entry = &full->e[blockIdx.x];
     } else {
-    // ---- copy tiles, straight from their class records (k_classify_tiles): no layout list, no classification, no barrier
-    const int t0 = rest * B_COPY_TILES;
-    const int bx = 4 * (tid & 31), by = 2 * (tid >> 5);
-    TileClass c[B_COPY_TILES];
-#pragma unroll
-    for (int k = 0; k < B_COPY_TILES; k++) {
-        c[k] = tc[min(t0 + k, tiles - 1)];
-        if (t0 + k >= tiles) c[k].kind = TC_SKIP;
-    }
-    u32 acc[B_COPY_TILES][8];
-    bool on[B_COPY_TILES];
-    bool aligned = true;  // (uniform) every texture tile of the group can be read 16 bytes at a time
-#pragma unroll
-    for (int k = 0; k < B_COPY_TILES; k++) {
-        const int tile = t0 + k, ty = tile / tiles_x;
-        on[k] = c[k].kind <= TC_TEXTURE && !((srgb_and_ablate >> 8) & 64) && (tile - ty * tiles_x) * B_TILE_W + bx < W && ty * B_TILE_H + by < H;
-        if (c[k].kind == TC_TEXTURE && ((((uintptr_t)c[k].base) & 15) != 0 || (c[k].pitch_or_px & 15) != 0)) aligned = false;
-        if ((W & 3) && (tile - ty * tiles_x) * B_TILE_W + B_TILE_W > W) aligned = false;  // the row's last block is two pixels wide
-    }
-    if (aligned) {
-        // straight-line: the texel loads of all the group's tiles are in flight together (a lane with nothing to read reads the
-        // tables instead — no branch between the loads); 1:1 blit of an opaque texture: decode -> encode is the identity
-        uint4 ra[B_COPY_TILES], rb[B_COPY_TILES];
-#pragma unroll
-        for (int k = 0; k < B_COPY_TILES; k++) {
-            const bool tex = on[k] && c[k].kind == TC_TEXTURE;
-            const u8 *r0 = tex ? c[k].base + b_off(by, c[k].pitch_or_px, bx * 4) : (const u8 *)tables;
-            const u8 *r1 = tex ? r0 + c[k].pitch_or_px : (const u8 *)tables;
-            ra[k] = g_ld_u32x4(r0);  // (global loads: a base from a record in memory is a generic pointer to the compiler — smr_internal.h)
-            rb[k] = g_ld_u32x4(r1);
-        }
-#pragma unroll
-        for (int k = 0; k < B_COPY_TILES; k++) {
-            const bool tex = c[k].kind == TC_TEXTURE;
-            const u32 fill = c[k].kind == TC_COLOUR ? c[k].pitch_or_px : 0u;
-            acc[k][0] = tex ? ra[k].x : fill; acc[k][1] = tex ? ra[k].y : fill; acc[k][2] = tex ? ra[k].z : fill; acc[k][3] = tex ? ra[k].w : fill;
-            acc[k][4] = tex ? rb[k].x : fill; acc[k][5] = tex ? rb[k].y : fill; acc[k][6] = tex ? rb[k].z : fill; acc[k][7] = tex ? rb[k].w : fill;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < B_COPY_TILES; k++) {
-            const u32 fill = c[k].kind == TC_COLOUR ? c[k].pitch_or_px : 0u;
-#pragma unroll
-            for (int q = 0; q < 8; q++) acc[k][q] = fill;
-            if (on[k] && c[k].kind == TC_TEXTURE) {
-                const u8 *r0 = c[k].base + b_off(by, c[k].pitch_or_px, bx * 4), *r1 = r0 + c[k].pitch_or_px;
-                const int tile = t0 + k, cols = W - ((tile - (tile / tiles_x) * tiles_x) * B_TILE_W + bx);  // >= 2
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                    if (q < cols) { acc[k][q] = g_ld_u32(r0 + 4 * q); acc[k][4 + q] = g_ld_u32(r1 + 4 * q); }
+        const int groups = (int)gridDim.x - n_banded;
+        const int run = (tiles + groups - 1) / groups;
+        t_begin = rest * run;
+        t_end = min(t_begin + run, tiles);
+        if (t_begin >= t_end) return;
+        // ---- copy tiles, straight from their class records (k_classify_tiles): no layout list, no classification, no barrier.
+        // c0 = this tile's record, c1 = the next one's (its texels are requested before this tile is converted), c2 = on its way;
+        // cur = this tile's texels, nxt = the next one's.
+        const bool ablate_copy = ((srgb_and_ablate >> 8) & 64) != 0;  // (profiling)
+        const bool planes_ok = planes_pair_aligned<NV>(yp, up, vp);
+        int t = t_begin;
+        const int ty = t / tiles_x;
+        int tx0 = (t - ty * tiles_x) * B_TILE_W, ty0 = ty * B_TILE_H;  // this tile's first pixel: computed once, stepped
+        TileClass c0 = tc[t], c1 = tc[min(t + 1, tiles - 1)], c2;
+        u32 cur[8];
+        copy_tile_texels(c0, tx0 + 4 * (tid & 31) < W && ty0 + 2 * (tid >> 5) < H && !ablate_copy, W - tx0, 4 * (tid & 31), 2 * (tid >> 5), tables, cur);
+#pragma unroll 1
+        for (;;) {
+            // (the lane's position is formed again for every tile: what is derived from it is not held in registers across the walk)
+            int ltid = tid;
+            B_KEEP_IN_LOOP(ltid);
+            const int bx = 4 * (ltid & 31), by = 2 * (ltid >> 5);
+            const int px0 = tx0 + bx, py0 = ty0 + by;
+            const bool inside = px0 < W && py0 < H;
+            const bool pair = planes_ok && tx0 + B_TILE_W <= W && ty0 + B_TILE_H <= H;  // (uniform) every lane holds a whole block
+            c2 = tc[min(t + 2, tiles - 1)];
+            // the next tile's texels, requested before this tile's arithmetic
+            u32 nxt[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+            const bool wrap = tx0 + B_TILE_W >= tiles_x * B_TILE_W;
+            const int nx0 = wrap ? 0 : tx0 + B_TILE_W, ny0 = wrap ? ty0 + B_TILE_H : ty0;
+            if (t + 1 < t_end) copy_tile_texels(c1, nx0 + bx < W && ny0 + by < H && !ablate_copy, W - nx0, bx, by, tables, nxt);
+            if (c0.kind <= TC_TEXTURE) {
+                if (inside && !ablate_copy) store_yuv_block<NV>(cur, px0, py0, W, yp, up, vp, pair);
+            } else if (c0.kind == TC_SAMPLED || c0.kind == TC_SELECT) {
+                later = true;  // (below, once the run's copies are on their way: those paths want the registers the walk holds)
+            } else if (c0.kind == TC_FULL && (int)c0.pitch_or_px + (int)(uintptr_t)c0.base > n_banded) {
+                left_out = true;
             }
-        }
-    }
+            // (TC_SKIP: wave A writes the tile; TC_FULL with a workgroup per band: nothing to do here)
+            if (++t >= t_end) break;
 #pragma unroll
-    for (int k = 0; k < B_COPY_TILES; k++) {
-        const int tile = t0 + k, ty = tile / tiles_x;
-        if (on[k]) store_yuv_block<NV>(acc[k], (tile - ty * tiles_x) * B_TILE_W + bx, ty * B_TILE_H + by, W, yp, up, vp);
-    }
-    // sampled tiles: one layer's record straight from the list in memory, eight independent pixels per thread
-#pragma unroll 1
-    for (int k = 0; k < B_COPY_TILES; k++) {
-        if (c[k].kind != TC_SAMPLED || ((srgb_and_ablate >> 8) & 32)) continue;  // (32: profiling, no sampled tiles)
-        __syncthreads();
-        for (int i = tid; i < SMR_TABLE_FLOATS; i += 256) s_tab[i] = tables[i];
-        __syncthreads();
-        const DevLayout L = load_uniform(&layouts_g[c[k].pitch_or_px]);
-        const int tile = t0 + k, ty = tile / tiles_x;
-        const int px0 = (tile - ty * tiles_x) * B_TILE_W + bx, py0 = ty * B_TILE_H + by;
-        if (px0 < W && py0 < H) {
-            u32 a[8];
-            composite_sampled_opaque_block(L, px0, py0, srgb_and_ablate & 1, s_tab, s_tab + 256, a);  // (column / row halves of the sample positions once each)
-            store_yuv_block<NV>(a, px0, py0, W, yp, up, vp);
+            for (int q = 0; q < 8; q++) cur[q] = nxt[q];
+            c0 = c1; c1 = c2;
+            tx0 = nx0; ty0 = ny0;
         }
+        if (!later && !left_out) return;
     }
-    // select tiles: every pixel a copy from the topmost listed layer whose pixel box holds it (records through scalar loads: the layer
-    // numbers are the workgroup's)
+    // ---- the run's sampled and select tiles as they are met (uniform).  Nothing of the walk above is alive here but the run itself.
+    if (later) {
 #pragma unroll 1
-    for (int k = 0; k < B_COPY_TILES; k++) {
-        if (c[k].kind != TC_SELECT) continue;
-        const int tile = t0 + k, ty = tile / tiles_x;
-        const int px0 = (tile - ty * tiles_x) * B_TILE_W + bx, py0 = ty * B_TILE_H + by;
-        u32 a[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-        u32 open_px = 0xffu;  // pixels no layer has claimed yet
-#pragma unroll 1
-        for (int q = 0; q < 4; q++) {
-            const u32 li = (c[k].pitch_or_px >> (8 * q)) & 0xffu;
-            if (li == 0xffu) break;  // (uniform)
-            const DevLayout &L = layouts_g[li];
-            const int lx0 = L.bx0, ly0 = L.by0, lx1 = L.bx1, ly1 = L.by1;
-            const bool colour = L.type != 0;
-            const u32 solid = L.solid_px;
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int px = px0 + (i & 3), py = py0 + (i >> 2);
-                if (((open_px >> i) & 1u) && px >= lx0 && px < lx1 && py >= ly0 && py < ly1) {
-                    a[i] = colour ? solid : aligned_texel(L, px, py);
-                    open_px &= ~(1u << i);
+        for (int t = t_begin; t < t_end; t++) {
+            const TileClass c = tc[t];
+            if (c.kind != TC_SAMPLED && c.kind != TC_SELECT) continue;
+            int ltid = tid;
+            B_KEEP_IN_LOOP(ltid);  // (as above)
+            const int ty = t / tiles_x, tx0 = (t - ty * tiles_x) * B_TILE_W, ty0 = ty * B_TILE_H;
+            const int px0 = tx0 + 4 * (ltid & 31), py0 = ty0 + 2 * (ltid >> 5);
+            const bool inside = px0 < W && py0 < H;
+            const bool pair = tx0 + B_TILE_W <= W && ty0 + B_TILE_H <= H && planes_pair_aligned<NV>(yp, up, vp);  // (uniform)
+            if (c.kind == TC_SAMPLED) {
+                // sampled tiles: one layer's record straight from the list in memory, eight independent pixels per thread
+                if ((srgb_and_ablate >> 8) & 32) continue;  // (32: profiling, no sampled tiles)
+                __syncthreads();
+                for (int i = ltid; i < SMR_TABLE_FLOATS; i += 256) s_tab[i] = tables[i];
+                __syncthreads();
+                const DevLayout L = load_uniform(&layouts_g[c.pitch_or_px]);
+                if (inside) {
+                    u32 a[8];
+                    composite_sampled_opaque_block(L, px0, py0, srgb_and_ablate & 1, s_tab, s_tab + 256, a);  // (column / row halves of the sample positions once each)
+                    store_yuv_block<NV>(a, px0, py0, W, yp, up, vp, pair);
                 }
+            } else if (c.kind == TC_SELECT) {
+                // select tiles: every pixel a copy from the topmost listed layer whose pixel box holds it (records through scalar loads: the
+                // layer numbers are the workgroup's)
+                u32 a[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+                u32 open_px = 0xffu;  // pixels no layer has claimed yet
+#pragma unroll 1
+                for (int q = 0; q < 4; q++) {
+                    const u32 li = (c.pitch_or_px >> (8 * q)) & 0xffu;
+                    if (li == 0xffu) break;  // (uniform)
+                    const DevLayout &L = layouts_g[li];
+                    const int lx0 = L.bx0, ly0 = L.by0, lx1 = L.bx1, ly1 = L.by1;
+                    const bool colour = L.type != 0;
+                    const u32 solid = L.solid_px;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        const int px = px0 + (i & 3), py = py0 + (i >> 2);
+                        if (((open_px >> i) & 1u) && px >= lx0 && px < lx1 && py >= ly0 && py < ly1) {
+                            a[i] = colour ? solid : aligned_texel(L, px, py);
+                            open_px &= ~(1u << i);
+                        }
+                    }
+                }
+                if (inside) store_yuv_block<NV>(a, px0, py0, W, yp, up, vp, pair);
             }
         }
-        if (px0 < W && py0 < H) store_yuv_block<NV>(a, px0, py0, W, yp, up, vp);
+        if (!left_out) return;
     }
-    // a tile that needs compositing and whose bands found no room (or not all of them) among the first workgroups (the host's bound was
-    // short): here, band after band
-    if (c[0].kind == TC_FULL && (int)c[0].pitch_or_px + (int)(uintptr_t)c[0].base > n_banded) {
-        full_entry = &full->e[c[0].pitch_or_px];
-        full_entries = (int)(uintptr_t)c[0].base;
-    }
-    if (B_COPY_TILES > 1 && c[B_COPY_TILES - 1].kind == TC_FULL && (int)c[B_COPY_TILES - 1].pitch_or_px + (int)(uintptr_t)c[B_COPY_TILES - 1].base > n_banded) {
-        const TileFull *e = &full->e[c[B_COPY_TILES - 1].pitch_or_px];
-        if (full_entry) { full_entry2 = e; full_entries2 = (int)(uintptr_t)c[B_COPY_TILES - 1].base; }
-        else { full_entry = e; full_entries = (int)(uintptr_t)c[B_COPY_TILES - 1].base; }
-    }
-    }
-    // (uniform; one band of a listed tile, or the bands of a tile — of each tile of the group — that the list's bound left out)
-#ifdef SMR_COMPOSE_NO_FULL  // profiling builds only: the compositing path compiled out (what the copy paths alone need in registers and time)
-    if (full_entry || full_entry2) return;
-#endif
+    // ---- compositing (uniform): one band of a listed tile, or — band after band — the bands of every tile of the run that the list's bound left
+    // out (the host's bound was short)
 #pragma unroll 1
-    for (int q = 0; q < 2; q++) {
-        const TileFull *e = q == 0 ? full_entry : full_entry2;
-        if (!e) break;
-        const int entries = q == 0 ? full_entries : full_entries2;
+    for (int t = t_begin;; t++) {
+        const TileFull *e;
+        int entries = 1;
+        if (rest < 0) {
+            e = &full->e[blockIdx.x];
+        } else {
+            if (t >= t_end) break;
+            const TileClass c = tc[t];
+            if (!(c.kind == TC_FULL && (int)c.pitch_or_px + (int)(uintptr_t)c.base > n_banded)) continue;
+            e = &full->e[c.pitch_or_px];
+            entries = (int)(uintptr_t)c.base;
+        }
+#ifndef SMR_COMPOSE_NO_FULL  // (profiling builds only: the compositing path compiled out — what the copy paths alone need in registers and time)
 #pragma unroll 1
         for (int j = 0; j < entries; j++) {
             if (rest >= 0 && (int)(e - full->e) + j < n_banded) continue;  // (that band has a workgroup of its own)
             const u32 bw = __builtin_amdgcn_readfirstlane(e[j].band);
             compose_full<NV, BIG>(&e[j], (int)(bw & 0xffu), (int)(bw >> 8), yp, up, vp, W, H, layouts_g, masks_g, n, n_masks, srgb_and_ablate, tables, tiles_x, s_tab);
         }
+#endif
+        if (rest < 0) break;
     }
 }
 

@@ -24,7 +24,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define dev_readfirstlane(x) __builtin_amdgcn_readfirstlane(x)
 #define dev_mfma_16x16x32_f16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 #define dev_wait_vmcnt0() __builtin_amdgcn_s_waitcnt(0x0f70)
-#define dev_mov_dpp_quad_swap(x) __builtin_amdgcn_mov_dpp((x), 0xb1, 0xf, 0xf, true) /* quad_perm [1,0,3,2] */
+// (dev_mov_dpp_quad_swap, quad_perm [1,0,3,2]: smr_internal.h — the compositor's paired stores use it too)
 #define dev_sched_barrier() __builtin_amdgcn_sched_barrier(0)
 // lanes of a wave exchanging data through LDS: the hardware runs a wave's LDS operations in order, so nothing is needed (the
 // builtin emits no instruction, it only keeps the compiler from moving LDS accesses across it); the emulator's lanes are threads

@@ -76,6 +76,7 @@ __device__ __forceinline__ u32 g_ld_u32(const void *p) { return *SMR_GLOBAL_PTR(
 __device__ __forceinline__ uint2 g_ld_u32x2(const void *p) { const g_u32x2 v = *SMR_GLOBAL_PTR(const g_u32x2, p); return make_uint2(v.x, v.y); }
 __device__ __forceinline__ uint4 g_ld_u32x4(const void *p) { const g_u32x4 v = *SMR_GLOBAL_PTR(const g_u32x4, p); return make_uint4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ void g_st_u32(void *p, u32 v) { *SMR_GLOBAL_PTR(u32, p) = v; }
+__device__ __forceinline__ void g_st_u32x2(void *p, u32 a, u32 b) { g_u32x2 v; v.x = a; v.y = b; *SMR_GLOBAL_PTR(g_u32x2, p) = v; }
 __device__ __forceinline__ void g_st_u32x3(void *p, u32 a, u32 b, u32 c) { g_u32x3 v; v.x = a; v.y = b; v.z = c; *SMR_GLOBAL_PTR(g_u32x3, p) = v; }
 __device__ __forceinline__ void g_st_u32x4(void *p, uint4 q) { g_u32x4 v; v.x = q.x; v.y = q.y; v.z = q.z; v.w = q.w; *SMR_GLOBAL_PTR(g_u32x4, p) = v; }
 // A wave-uniform record of a table no kernel writes while this one runs (weight band metadata): read through the constant address space, i.e. by
@@ -85,11 +86,15 @@ __device__ __forceinline__ int2 g_ld_uniform_i32x2(const void *p) { const g_i32x
 // A wave-uniform value stays in the scalar registers it is in: the compiler otherwise re-reads a kernel-argument field wherever it is used
 // (a scalar load and a wait for it inside a loop) instead of keeping it.
 #define SMR_KEEP_SCALAR(x) asm volatile("" : "+s"(x))
+// Lanes l and l ^ 1 of a wave exchange a dword (v_mov_b32 with DPP quad_perm [1,0,3,2]): every lane of the wave takes part.  The lane
+// emulator's twin is tests/emu/emu_device.h's function of the same name.
+#define dev_mov_dpp_quad_swap(x) __builtin_amdgcn_mov_dpp((x), 0xb1, 0xf, 0xf, true)
 #else  // (host code and the lane emulator: plain accesses)
 static inline u32 g_ld_u32(const void *p) { return *(const u32 *)p; }
 static inline uint2 g_ld_u32x2(const void *p) { return *(const uint2 *)p; }
 static inline uint4 g_ld_u32x4(const void *p) { return *(const uint4 *)p; }
 static inline void g_st_u32(void *p, u32 v) { *(u32 *)p = v; }
+static inline void g_st_u32x2(void *p, u32 a, u32 b) { ((u32 *)p)[0] = a; ((u32 *)p)[1] = b; }
 static inline void g_st_u32x3(void *p, u32 a, u32 b, u32 c) { ((u32 *)p)[0] = a; ((u32 *)p)[1] = b; ((u32 *)p)[2] = c; }
 static inline void g_st_u32x4(void *p, uint4 q) { *(uint4 *)p = q; }
 static inline int2 g_ld_uniform_i32x2(const void *p) { return *(const int2 *)p; }
