@@ -12,7 +12,8 @@
        past the last transition and for the last frame of such a run of frames at rest, not for every frame that is.
 tests/test_scene_walk.py drives the C++ scene engine and the oracle's scene state through these and asserts what the walks cover;
 tests/test_gpu_scene_walk.py drives renderers.  `walk_nodes(seed)` is the smaller walk without transitions whose scenes also hold a blur
-Shader node, a static Image and a Text label (part 2 of the GPU module).
+Shader node, a static Image and a Text label (part 2 of the GPU module).  `walk_formats(seed)` is the walk of `walk`'s vocabulary over what a renderer
+can be fed: a frame spec's format is any base format of smr_frame_format, a Y'CbCr one with its colour matrix behind an "@" ("p010@bt2020").
 
 Scenes stay inside what tests/scene_json.to_oracle reads: View / Rescaler / Tiles over input streams, three layout levels deep at most.  A
 scene is built from two generators, one for the STRUCTURE (kinds, child counts, which optional fields exist, component ids from a pool of
@@ -752,12 +753,343 @@ def walk_nodes(seed, frames=25):
     return _NodeWalk(seed, frames, transitions=False, scene_of=_node_scene).run()
 
 
+# ------------------------------------------------------------------------------------------------- the walk of input formats, matrices and alpha
+FORMAT_SEEDS = [201, 202, 203, 204, 205, 206, 207, 208]   # odd: MODE_CPU_OPTIMIZED contexts (the oracle at srgb=False), even: MODE_GPU_OPTIMIZED
+# the base formats, by their smr_frame_format value (include/smr.h)
+BASE_FORMATS = ["yuv420", "yuv422", "yuv444", "yuvj420", "uyvy422", "yuyv422", "nv12", "bgra", "argb", "rgba", "p010", "yuv420p10", "yuv422p10", "p210", "v210"]
+MATRICES = [None, "bt601", "bt2020"]            # None: untagged (BT.709); carried in a spec's format string as "p010@bt2020"
+ODD_SIZES = [(37, 21), (38, 21), (50, 22), (131, 75)]   # odd widths and heights; widths that fill neither a v210 group of 6 nor 48 pixels
+FORMAT_SIZES = INPUT_SIZES + ODD_SIZES
+ALPHA_FORMATS = ["bgra", "argb", "rgba"]
+YCBCR_FORMATS = [f for f in BASE_FORMATS if f not in ALPHA_FORMATS]
+RGB12_FORMATS = ["yuv420", "yuvj420", "nv12"]                 # 8-bit 4:2:0: what the block converter and the RGB12 node take
+OTHER_8BIT_FORMATS = ["yuv422", "yuv444", "uyvy422", "yuyv422"]
+PACKED_8BIT_FORMATS = ["uyvy422", "yuyv422"]                  # one texel per pixel pair: an even width
+HI_FORMATS = ["p010", "yuv420p10", "yuv422p10", "p210", "v210"]
+CONVERTER_FAMILIES = {"yuv420": "block420", "yuvj420": "block420", "nv12": "block420", "yuv422": "planar", "yuv444": "planar", "uyvy422": "packed",
+                      "yuyv422": "packed", "bgra": "swizzle", "argb": "swizzle", "p010": "hi420", "yuv420p10": "hi420", "yuv422p10": "hi422",
+                      "p210": "hi422", "v210": "v210"}   # (rgba: premultiplied on ingest, none of the seven)
+
+
+def split_format(fmt):
+    """"p010@bt2020" -> ("p010", "bt2020"); "nv12" -> ("nv12", None)"""
+    base, _, matrix = fmt.partition("@")
+    return base, matrix or None
+
+
+def join_format(base, matrix):
+    return base if matrix is None else f"{base}@{matrix}"
+
+
+def format_mode(seed):
+    return "cpu_optimized" if seed % 2 else "gpu_optimized"
+
+
+def format_accepts(base, w, h):
+    return w % 2 == 0 if base in PACKED_8BIT_FORMATS else True
+
+
+def alpha_everywhere_255(spec):
+    """One BGRA / ARGB / RGBA frame in four is opaque in every pixel."""
+    return spec[3] % 4 == 0
+
+
+def _format_scene(struct_seed, param_seed, W, H):
+    """build_scene, and over a View root often one more child: an absolutely positioned Rescaler "ov" over its siblings, so that an input
+    with alpha is composited over other inputs (a wrongly opaque hand-off shows in the picture)."""
+    js = build_scene(struct_seed, param_seed, W, H)
+    rs, rp = Rng(struct_seed ^ 0xF0F0), Rng(param_seed ^ 0x0F0F)
+    if js["type"] == "view" and rs.chance(0.7):
+        js["children"].append({"type": "rescaler", "id": "ov", "top": rp.quarter(0, H * 0.3), "left": rp.quarter(0, W * 0.3), "width": rp.quarter(W * 0.3, W * 0.7),
+                               "height": rp.quarter(H * 0.3, H * 0.7), "mode": rp.pick(["fit", "fill"]), "child": {"type": "input_stream", "input_id": rp.pick(INPUT_IDS)}})
+    return js
+
+
+def overlay_input(scene):
+    for c in scene.get("children", []):
+        if c.get("id") == "ov" and c["type"] == "rescaler":
+            return c["child"]["input_id"]
+    return None
+
+
+class _FormatWalk(_Walk):
+    def __init__(self, seed, frames_target):
+        super().__init__(seed, frames_target, scene_of=_format_scene)
+        self.seed = seed
+
+    def new_frame(self, size=None, fmt=None, among=None):
+        r = self.r
+        if fmt is None:
+            pool = [b for b in (among or BASE_FORMATS) if size is None or format_accepts(b, *size)]
+            base = r.pick(pool)
+            fmt = join_format(base, r.pick(MATRICES) if base in YCBCR_FORMATS else None)
+        if size is None:
+            size = r.pick([s for s in FORMAT_SIZES if format_accepts(split_format(fmt)[0], *s)])
+        return [fmt, size[0], size[1], r.below(1 << 30)]
+
+    def seed_with_alpha(self):
+        s = self.r.below(1 << 30)
+        return s + 1 if s % 4 == 0 else s
+
+    def shown(self):
+        return [i for o in self.out.values() for i in input_ids_of(o["scene"]) if i in self.registered and self.frames.get(i) is not None]
+
+    def phase_formats(self, how):
+        """One input id changes between two consecutive renders: (a) opaque Y'CbCr <-> a format with alpha, (b) an RGB12-capable format <-> another
+        8-bit Y'CbCr one, (c) 8 <-> 10 bits, all at the same size and back again; (d) nothing but the matrix, on new and on identical
+        content; (e) the same format at a new size, an odd one first."""
+        r = self.r
+        shown = self.shown()
+        k = r.pick(shown) if shown else self.registered[0]
+        f = self.frames.get(k) or self.new_frame()
+        size = (f[1], f[2])
+        base, matrix = split_format(f[0])
+        if how in "abc":
+            pools = {"a": (YCBCR_FORMATS, ALPHA_FORMATS), "b": (RGB12_FORMATS, OTHER_8BIT_FORMATS), "c": (RGB12_FORMATS + OTHER_8BIT_FORMATS, HI_FORMATS)}[how]
+            if base not in pools[0] and base not in pools[1]:
+                f = self.new_frame(size, among=pools[0])
+                self.frames[k] = f
+                self.set_frames()
+                self.render()
+                base = split_format(f[0])[0]
+            there = pools[1] if base in pools[0] else pools[0]
+            g = self.new_frame(size, among=there)
+            if how == "a":
+                (g if there is ALPHA_FORMATS else f)[3] = self.seed_with_alpha()
+                if there is not ALPHA_FORMATS:   # (the frame with alpha is the earlier one: shown once more with alpha for certain)
+                    self.frames[k] = f
+                    self.set_frames()
+                    self.render()
+            self.frames[k] = g
+            self.set_frames()
+            self.render()
+            self.frames[k] = [f[0], f[1], f[2], self.seed_with_alpha() if how == "a" else r.below(1 << 30)]
+            self.set_frames()
+            self.render()
+        elif how == "d":
+            if base not in YCBCR_FORMATS:
+                f = self.new_frame(size, among=YCBCR_FORMATS)
+                self.frames[k] = f
+                self.set_frames()
+                self.render()
+                base, matrix = split_format(f[0])
+            others = [m for m in MATRICES if m != matrix]
+            self.frames[k] = [join_format(base, others[0]), f[1], f[2], r.below(1 << 30)]   # new content under a new matrix
+            self.set_frames()
+            self.render()
+            self.frames[k] = [join_format(base, others[1]), f[1], f[2], self.frames[k][3]]  # the same content under the third
+            self.set_frames()
+            self.render()
+        else:
+            sizes = [s for s in ODD_SIZES if s != size and format_accepts(base, *s)]
+            self.frames[k] = [f[0], *r.pick(sizes), r.below(1 << 30)]
+            self.set_frames()
+            self.render()
+            self.frames[k] = [f[0], *r.pick([s for s in FORMAT_SIZES if s != tuple(self.frames[k][1:3]) and format_accepts(base, *s)]), r.below(1 << 30)]
+            self.set_frames()
+            self.render()
+
+    def phase_mix(self, how):
+        """Every input gets a new frame: two of one base format under different matrices, or three converter families at once; then
+        the tags move to other inputs."""
+        r = self.r
+        ids = r.shuffled(INPUT_IDS)
+        if how == "pair":
+            base = r.pick(YCBCR_FORMATS)
+            tags = r.shuffled(MATRICES)
+            bases = [base, base, r.pick([b for b in YCBCR_FORMATS if CONVERTER_FAMILIES[b] != CONVERTER_FAMILIES[base]]), r.pick(BASE_FORMATS)]
+        else:
+            fams = r.shuffled(sorted(set(CONVERTER_FAMILIES.values())))[:4]
+            bases = [r.pick([b for b in BASE_FORMATS if CONVERTER_FAMILIES.get(b) == fam]) for fam in fams]
+            tags = [r.pick(MATRICES) for _ in range(3)]
+        for turn in range(3):
+            for i, (k, b) in enumerate(zip(ids, bases)):
+                tag = tags[(i + turn) % len(tags)] if b in YCBCR_FORMATS else None
+                old = self.frames.get(k)
+                if turn and old is not None:   # the same planes' geometry, the tag of its neighbour, new content on every second input
+                    self.frames[k] = [join_format(b, tag), old[1], old[2], old[3] if i % 2 else r.below(1 << 30)]
+                else:
+                    self.frames[k] = self.new_frame(fmt=join_format(b, tag))
+            self.set_frames()
+            self.render()
+
+    def class_boxes(self):
+        """(input id, size) of every Rescaler of a live scene whose box is one of the first four INPUT_SIZES times 1.5, 2 or 3 and holds an input stream:
+        with a frame of that size inside, the resample plan sits in a class window of the matrix-core resampler."""
+        out = []
+        for o in self.out.values():
+            for c in _layout_components(o["scene"]):
+                if c["type"] == "rescaler" and c["child"]["type"] == "input_stream" and "width" in c and "height" in c:
+                    out += [(c["child"]["input_id"], s) for s in INPUT_SIZES[:4] for f in (1.5, 2, 3) if (c["width"], c["height"]) == (s[0] * f, s[1] * f)]
+        return out
+
+    def phase_node(self):
+        """One source index between the node textures the resampler reads: an 8-bit 4:2:0 frame in a class window (the RGB12 node where the library
+        chooses it), then at the same size another 8-bit format, 10 bits, alpha (the RGBA8 node), 4:2:0 under another matrix, and a new plan."""
+        r = self.r
+        for _ in range(12):
+            boxes = self.class_boxes()
+            if boxes:
+                break
+            self.fresh("a")
+        if not boxes:
+            return self.render()
+        k, size = r.pick(boxes)
+        self.register(k)
+        tags = r.shuffled(MATRICES)
+        for i, pool in enumerate([RGB12_FORMATS, OTHER_8BIT_FORMATS, RGB12_FORMATS, HI_FORMATS, RGB12_FORMATS, ALPHA_FORMATS, RGB12_FORMATS]):
+            base = r.pick(pool)
+            self.frames[k] = [join_format(base, tags[i % 3] if base in YCBCR_FORMATS else None), size[0], size[1], self.seed_with_alpha()]
+            self.set_frames()
+            self.render()
+        self.moved(r.pick(sorted(self.out)), with_transition=False)
+        self.render()
+
+    def phase_overlay(self):
+        """A scene with the overlay, its input in a format with alpha, the input below it changing."""
+        r = self.r
+        for _ in range(12):
+            if overlay_input(self.out["a"]["scene"]) is not None:
+                break
+            self.fresh("a")
+        k = overlay_input(self.out["a"]["scene"])
+        if k is None:
+            return self.render()
+        self.register(k)
+        size = r.pick(FORMAT_SIZES)
+        for _ in range(3):
+            self.frames[k] = [r.pick(ALPHA_FORMATS), size[0], size[1], self.seed_with_alpha()]
+            for j in self.shown():
+                if j != k and r.chance(0.5):
+                    self.frames[j] = self.new_frame()
+            self.set_frames()
+            self.render()
+
+    def run(self):
+        r = self.r
+        for k in INPUT_IDS[:3]:
+            self.register(k)
+        for i, k in enumerate(INPUT_IDS):   # (the first frames of consecutive seeds go through the base formats three at a time)
+            self.frames[k] = self.new_frame(among=[BASE_FORMATS[(3 * self.seed + i) % len(BASE_FORMATS)]]) if i < 3 else None
+        self.set_frames()
+        W, H = r.pick(OUTPUT_SIZES)
+        self.fresh("a", W, H, "yuv420")
+        self.render()
+        must = ["b_on", "transition", "a", "b", "c", "d", "e", "pair", "families", "overlay", "node", "content", "b_off", "absent", "stale", "registry", "settle", "tiles",
+                "resolution", "inputs"]
+        must = must[:2] + r.shuffled(must[2:])
+        while must or self.renders < self.target - 3:
+            ph = must.pop(0) if must else r.pick(["a", "b", "c", "d", "e", "pair", "families", "overlay", "node", "transition", "inputs"])
+            if ph == "b_on":
+                if "b" not in self.out:
+                    self.phase_b()
+            elif ph == "b_off":
+                if "b" not in self.out:
+                    self.phase_b()
+                self.render()
+                self.unregister_output("b")
+                self.render()
+            elif ph == "transition":
+                self.phase_transition(r.pick(sorted(self.out)))
+            elif ph in ("a", "b", "c", "d", "e"):
+                self.phase_formats(ph)
+            elif ph in ("pair", "families"):
+                self.phase_mix(ph)
+            elif ph == "overlay":
+                self.phase_overlay()
+            elif ph == "node":
+                self.phase_node()
+            elif ph == "tiles":
+                self.phase_tiles(r.pick(sorted(self.out)))
+            elif ph == "settle":
+                self.phase_rest(3, settled=True)
+            elif ph == "content":
+                self.phase_content()
+            elif ph == "inputs":
+                self.phase_inputs()
+            elif ph == "absent":
+                self.phase_inputs(1)
+            elif ph == "stale":
+                self.phase_inputs(2)
+            elif ph == "registry":
+                self.phase_registry()
+            elif ph == "resolution":
+                self.phase_resolution()
+        if "b" in self.out:
+            self.unregister_output("b")
+        self.phase_rest(3, settled=True)
+        return self.ops
+
+
+def walk_formats(seed, frames=30):
+    """The walk over what a renderer can be fed: every base format, the three matrices, odd and ragged sizes, alpha over other inputs."""
+    return _FormatWalk(seed, frames).run()
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------- helpers
+def _alpha_field(w, h, seed):
+    """Alpha 0 .. 255 with runs of 0 and of 255 (a dozen pixels along a row); 255 everywhere on one frame in four."""
+    import numpy as np
+    yy, xx = np.mgrid[0:h, 0:w]
+    if seed % 4 == 0:
+        return np.full((h, w), 255, np.int64)
+    return np.clip((xx * 5 + yy * 3 + seed % 251) % 384 - 64, 0, 255)
+
+
+def _format_planes(base, w, h, seed):
+    """The planes of the formats the first walks do not use: the same gradients under noise; 10-bit codes with their low two bits in use and seeded
+    junk in every bit the format ignores."""
+    import numpy as np
+    from tests import hi422_model
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    if base in ALPHA_FORMATS:
+        a = _alpha_field(w, h, seed)
+        c = [np.clip((xx * (3 + i) + yy * (2 + i) + seed % (89 + i)) % 256 + rng.integers(-24, 25, (h, w)), 0, 255) for i in range(3)]
+        if base == "rgba":   # straight alpha
+            return [np.ascontiguousarray(np.stack(c + [a], -1).astype(np.uint8))]
+        r_, g_, b_ = [ci * a // 255 for ci in c]   # premultiplied: colour <= alpha
+        order = [b_, g_, r_, a] if base == "bgra" else [a, r_, g_, b_]
+        return [np.ascontiguousarray(np.stack(order, -1).astype(np.uint8))]
+    y = np.clip(16 + (xx * 3 + yy * 2 + seed % 97) % 219 + rng.integers(-24, 25, (h, w)), 16, 235)
+    if base in ("yuv444",):
+        ch, cw = h, w
+    elif base in ("yuv422", "yuv422p10", "p210"):
+        ch, cw = h, w // 2
+    elif base in PACKED_8BIT_FORMATS or base == "v210":
+        ch, cw = h, (w + 1) // 2
+    else:
+        ch, cw = h // 2, w // 2
+    cy, cx = np.mgrid[0:ch, 0:cw]
+    u = np.clip(128 + 60 * np.sin(cx / 7.0 + seed % 13) + rng.integers(-12, 13, (ch, cw)), 16, 240).astype(np.int64)
+    v = np.clip(128 + 60 * np.cos(cy / 5.0 + seed % 11) + rng.integers(-12, 13, (ch, cw)), 16, 240).astype(np.int64)
+    if base in ("yuv422", "yuv444"):
+        return [y.astype(np.uint8), u.astype(np.uint8), v.astype(np.uint8)]
+    if base == "uyvy422":
+        return [np.ascontiguousarray(np.stack([u, y[:, 0::2], v, y[:, 1::2]], -1).astype(np.uint8))]
+    if base == "yuyv422":
+        return [np.ascontiguousarray(np.stack([y[:, 0::2], u, y[:, 1::2], v], -1).astype(np.uint8))]
+    # 10 bits: the byte's code times four plus two more bits
+    y, u, v = (c * 4 + rng.integers(0, 4, c.shape) for c in (y, u, v))
+    junk = lambda shape: rng.integers(0, 64, shape)   # noqa: E731
+    if base in ("p010", "p210"):    # the code in the high ten bits, junk in the low six
+        uv = np.stack([u, v], -1)
+        return [((y << 6) | junk(y.shape)).astype(np.uint16), np.ascontiguousarray(((uv << 6) | junk(uv.shape)).astype(np.uint16))]
+    if base in ("yuv420p10", "yuv422p10"):   # the code in the low ten bits, junk in the high six
+        return [(c | (junk(c.shape) << 10)).astype(np.uint16) for c in (y, u, v)]
+    assert base == "v210", base
+    n = hi422_model.groups(w)
+    return [hi422_model.v210_pack(y, u, v, junk=rng.integers(0, 4, (h, 4 * n)), beyond=rng.integers(0, 1024, (h, 6 * n)))]
+
+
 def frame_planes(spec):
     """[format, w, h, content_seed] -> the planes of that frame (numpy, made on demand): gradients under noise of +-24 codes, so a stale or
-    misplaced tile is many LSB wrong."""
+    misplaced tile is many LSB wrong.  A matrix tag ("nv12@bt601") changes no plane."""
     import numpy as np
     fmt, w, h, seed = spec
+    fmt = split_format(fmt)[0]
+    if fmt not in INPUT_FORMATS:
+        return _format_planes(fmt, w, h, seed)
     rng = np.random.default_rng(seed)
     yy, xx = np.mgrid[0:h, 0:w]
     lo, hi = (0, 255) if fmt == "yuvj420" else (16, 235)

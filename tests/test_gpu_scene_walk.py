@@ -40,6 +40,25 @@ Kernels the twelve walks reached on that run (smr_debug_kernel_launches, the def
 resampler 1083, the 4:2:0 block converter 1334; with direct_output on 49 resampler launches carried direct-output jobs; the shard moved
 489 gathers.  The general resampling passes, the f32 ingest kernel and the general compositor were not reached by these seeds: they stay with
 their own zoos (tests/test_gpu_parity.py, tests/test_gpu_fused.py, tests/test_gpu_compose_zoo.py).
+
+The third walk (tests/scene_walk.walk_formats: all fifteen base formats, the three matrices, odd and ragged sizes, BGRA / ARGB / RGBA frames with alpha over
+other inputs, an input id changing format, depth, matrix, alpha or size between two renders, a sixth of the frame specs in caller memory over torch
+buffers of the tightest pitch; odd seeds in MODE_CPU_OPTIMIZED with the oracle at srgb=False) makes all three comparisons with the same bars.  The node of a
+frame with a matrix tag or of 10 bits is tests/color_matrix_model.node_rgba (the oracle has no such converter; tests/test_color_matrix_model.py holds the
+model to the oracle at BT.709, the device converters are held to it byte for byte by tests/test_gpu_color_matrix.py and the 10-bit modules).  Its pools on
+an MI355X:
+  seed 201 (cpu): 1.000000 / 1.000000 / 1.000000  (2724780 luma bytes, worst 0 LSB; 12 frames in caller memory; converter launches 136, of them the 4:2:0 block converter 60)
+  seed 202 (gpu): 0.999997 / 0.999996 / 1.000000  (1908672 luma bytes, worst 1 LSB; 11 frames in caller memory; converter launches 112, of them the 4:2:0 block converter 31)
+  seed 203 (cpu): 1.000000 / 1.000000 / 1.000000  (5700740 luma bytes, worst 0 LSB; 8 frames in caller memory; converter launches 159, of them the 4:2:0 block converter 57)
+  seed 204 (gpu): 0.999994 / 0.999997 / 0.999992  (3667716 luma bytes, worst 1 LSB; 13 frames in caller memory; converter launches 326, of them the 4:2:0 block converter 126)
+  seed 205 (cpu): 1.000000 / 1.000000 / 1.000000  (3732480 luma bytes, worst 0 LSB; 8 frames in caller memory; converter launches 88, of them the 4:2:0 block converter 25)
+  seed 206 (gpu): 0.999994 / 0.999993 / 0.999995  (3526648 luma bytes, worst 1 LSB; 9 frames in caller memory; converter launches 260, of them the 4:2:0 block converter 88)
+  seed 207 (cpu): 1.000000 / 1.000000 / 1.000000  (5305260 luma bytes, worst 0 LSB; 8 frames in caller memory; converter launches 227, of them the 4:2:0 block converter 53)
+  seed 208 (gpu): 0.999981 / 0.999998 / 0.999984  (2270924 luma bytes, worst 1 LSB; 11 frames in caller memory; converter launches 111, of them the 4:2:0 block converter 73)
+Launches of the default renderer over the eight seeds: compose_output 690, frame_to_rgba 1419, frame_to_rgba_420 513, ingest_wave_rgba 533, resample_general 20: converters other than the 4:2:0 block
+converter ran 906 times, and seed 204 reached the general resampling passes (20 launches).  A MODE_CPU_OPTIMIZED walk has no resampler (every byte was the
+oracle's).  A traced build of the same walks showed the RGB12 node and the RGBA8 node alternating on one source index at one size in seeds
+202, 204 and 206, for 8-bit 4:2:0 and 10-bit 4:2:2 frames.  These walks, and 51 further seeds run once, found no difference.
 """
 import ctypes as C
 import json
@@ -48,7 +67,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from tests import refpipe, scene_walk as SW, scenes
+from tests import color_matrix_model as cmm, refpipe, scene_walk as SW, scenes
 
 # (an absent input has size 0 x 0: the reference's layout arithmetic divides by it, and so does the oracle's)
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore:invalid value encountered:RuntimeWarning"),
@@ -76,23 +95,65 @@ def _planes(spec):
     return _planes_cache[key]
 
 
-def _node(spec):
-    """The oracle's node texture of a frame."""
-    key = tuple(spec)
+_ORACLE_PLANAR = {"yuv420": orc.YUV420, "yuv422": orc.YUV422, "yuv444": orc.YUV444, "yuvj420": orc.YUVJ420}
+_MATRIX = {None: cmm.BT709, "bt601": cmm.BT601, "bt2020": cmm.BT2020_NCL}
+
+
+def _node(spec, srgb=True):
+    """The oracle's node texture of a frame: its own converters for the untagged 8-bit formats; for a frame with a matrix tag or of 10 bits, where the
+    oracle has no converter, tests/color_matrix_model.py (held to the oracle at BT.709 by tests/test_color_matrix_model.py)."""
+    key = tuple(spec) + (srgb,)
     if key not in _node_cache:
         if len(_node_cache) > 256:
             _node_cache.clear()
         fmt, w, h, _ = spec
+        base, matrix = SW.split_format(fmt)
         p = _planes(spec)
-        if fmt == "nv12":
-            _node_cache[key] = orc.nv12_to_rgba(p[0], p[1], w, h)
+        if matrix is not None or base in SW.HI_FORMATS:
+            node = cmm.node_rgba(SW.BASE_FORMATS.index(base), w, h, p, _MATRIX[matrix])
+        elif base == "nv12":
+            node = orc.nv12_to_rgba(p[0], p[1], w, h)
+        elif base in _ORACLE_PLANAR:
+            node = orc.planar_yuv_to_rgba(p[0], p[1], p[2], w, h, _ORACLE_PLANAR[base])
+        elif base in SW.PACKED_8BIT_FORMATS:
+            node = orc.interleaved422_to_rgba(p[0], w, h, 0 if base == "uyvy422" else 1)
+        elif base in ("bgra", "argb"):
+            node = orc.swizzle_to_rgba(p[0], w, h, 0 if base == "bgra" else 1)
         else:
-            _node_cache[key] = orc.planar_yuv_to_rgba(p[0], p[1], p[2], w, h, orc.YUVJ420 if fmt == "yuvj420" else orc.YUV420)
+            assert base == "rgba", base
+            node = orc.add_premultiplied_alpha(p[0], srgb)
+        _node_cache[key] = node
     return _node_cache[key]
 
 
 def _frame_format(hip, fmt):
-    return {"yuv420": hip.FRAME_PLANAR_YUV420, "yuvj420": hip.FRAME_PLANAR_YUVJ420, "nv12": hip.FRAME_NV12}[fmt]
+    """The smr_frame.format of a spec's format string: the base format and, behind an "@", its matrix (SMR_FRAME_WITH_MATRIX)."""
+    base, matrix = SW.split_format(fmt)
+    tag = {None: hip.MATRIX_BT709, "bt601": hip.MATRIX_BT601, "bt2020": hip.MATRIX_BT2020_NCL}[matrix]
+    return hip.frame_format(SW.BASE_FORMATS.index(base), tag)
+
+
+def _torch():
+    try:
+        import torch
+        return torch if torch.cuda.is_available() else None
+    except ImportError:
+        return None
+
+
+def _wrapped_frame(torch, ctx, fmt, w, h, planes):
+    """The frame over torch buffers with the tightest pitch a wrapped plane may have (its rows' bytes rounded up to 4), each exactly pitch * rows
+    long: -> (frame, buffers to keep alive)."""
+    bufs, pairs = [], []
+    for p in planes:
+        rows = np.ascontiguousarray(p).view(np.uint8).reshape(p.shape[0], -1)
+        pitch = (rows.shape[1] + 3) // 4 * 4
+        buf = torch.zeros((pitch * rows.shape[0],), dtype=torch.uint8, device="cuda")
+        buf.view(rows.shape[0], pitch)[:, :rows.shape[1]] = torch.from_numpy(rows).cuda()
+        bufs.append(buf)
+        pairs.append((buf.data_ptr(), pitch))
+    torch.cuda.synchronize()
+    return ctx.wrapped_frame(fmt, w, h, pairs), bufs
 
 
 def _logo():
@@ -106,27 +167,28 @@ def _logo():
 class Rig:
     """One renderer configuration with its own contexts and its own uploads."""
 
-    def __init__(self, hip, kind, nodes=False):
+    def __init__(self, hip, kind, nodes=False, mode=None, wrap=False):
         from smelter_amd.renderer import Renderer
-        self.hip, self.kind, self.nodes = hip, kind, nodes
-        self.ctx = hip.Context(0)
+        self.hip, self.kind, self.nodes, self.wrap = hip, kind, nodes, wrap
+        self.mode = hip.MODE_GPU_OPTIMIZED if mode is None else mode
+        self.ctx = hip.Context(0, self.mode)
         self.more = []
         if kind == "options":
             self.ctx.set_direct_output(True)
             self.ctx.set_compose_select(False)
             self.ctx.set_compact_nodes(False)
         if kind == "lanes":
-            self.more = [hip.Context(0), hip.Context(0)]
+            self.more = [hip.Context(0, self.mode), hip.Context(0, self.mode)]
             self.r = Renderer(self.ctx, lanes=self.more)
         elif kind == "shard":
-            self.more = [hip.Context(0)]
+            self.more = [hip.Context(0, self.mode)]
             self.r = Renderer(self.ctx, shards=self.more)
         else:
             self.r = Renderer(self.ctx)
         if nodes:
             self.r.register_image(SW.IMAGE_ID, _logo())
             self.r.register_shader(SW.SHADER_ID)
-        self.registered, self.frames, self.made, self.held = [], {}, {}, []
+        self.registered, self.frames, self.made, self.held, self.caller_memory = [], {}, {}, [], []
 
     def close(self):
         self.r.sync()
@@ -163,7 +225,12 @@ class Rig:
         ctx = self.r.input_context(iid) if self.kind == "shard" and iid in self.registered else self.ctx
         key = (ctx.handle.value, tuple(spec))
         if key not in self.made:   # (never destroyed before close: frames in flight may still read them)
-            self.made[key] = ctx.frame(_frame_format(self.hip, spec[0]), spec[1], spec[2], _planes(spec))
+            torch = _torch() if self.wrap and spec[3] % 6 == 0 else None
+            if torch is not None:  # a sixth of the format walk's frames live in caller memory (owned frames where there is no torch)
+                self.made[key], bufs = _wrapped_frame(torch, ctx, _frame_format(self.hip, spec[0]), spec[1], spec[2], _planes(spec))
+                self.caller_memory.append(bufs)
+            else:
+                self.made[key] = ctx.frame(_frame_format(self.hip, spec[0]), spec[1], spec[2], _planes(spec))
         return self.made[key]
 
     def render(self, op):
@@ -181,9 +248,9 @@ class Rig:
         return {self.r._outs[i].output_id.decode(): self.r.output(i) for i in range(n)}
 
 
-def _fresh_render(hip, update_op, registered, frames, render_op, nodes=False):
+def _fresh_render(hip, update_op, registered, frames, render_op, nodes=False, mode=None, wrap=False):
     """A brand-new renderer on a brand-new context: that output's last update, the current frames, one render."""
-    rig = Rig(hip, "plain", nodes)
+    rig = Rig(hip, "plain", nodes, mode, wrap)
     try:
         for iid in registered:
             rig.apply({"op": "register_input", "input_id": iid})
@@ -202,8 +269,11 @@ def _plane_names(fmt):
     return ["Y", "UV"] if fmt == "nv12" else ["Y", "U", "V"]
 
 
-def _run_walk(hip, seed, ops, tmp_path, oracle_on, nodes, kinds=KINDS):
-    rigs = {k: Rig(hip, k, nodes) for k in kinds}
+def _run_walk(hip, seed, ops, tmp_path, oracle_on, nodes, kinds=KINDS, mode=None, wrap=False, stats=None):
+    """mode: the rendering mode of every context (the four rigs', the fresh renderers') and of the oracle; wrap: frame specs whose content seed is a
+    multiple of 6 live in caller memory; stats: a dict that receives the default rig's kernel launch counts."""
+    srgb = mode is None or mode == hip.MODE_GPU_OPTIMIZED
+    rigs = {k: Rig(hip, k, nodes, mode, wrap) for k in kinds}
     witness = SW.OracleOutputs() if oracle_on else None
     last_update, registered, frames = {}, [], {}
     pools = {p: [0, 0] for p in "YUV"}   # identical bytes, bytes
@@ -268,9 +338,9 @@ def _run_walk(hip, seed, ops, tmp_path, oracle_on, nodes, kinds=KINDS):
                 mine[oid] = (fmt, a)
                 if witness:
                     W, H = last_update[oid]["width"], last_update[oid]["height"]
-                    layouts = witness.layouts(oid, op["pts_ns"], vis, srgb=True)
-                    textures = [_node(vis[i]) if i in vis else None for i in witness.inputs[oid]]
-                    rgba = refpipe.layout_node_render(layouts, textures, W, H, srgb=True, omp=True)
+                    layouts = witness.layouts(oid, op["pts_ns"], vis, srgb=srgb)
+                    textures = [_node(vis[i], srgb) if i in vis else None for i in witness.inputs[oid]]
+                    rgba = refpipe.layout_node_render(layouts, textures, W, H, srgb=srgb, omp=True)
                     want = list(orc.rgba_to_nv12(rgba)) if fmt == "nv12" else list(orc.rgba_to_planar_yuv(rgba, orc.YUV420, omp=True))
                     for name, g, w_ in zip(_plane_names(fmt), a, want):
                         d = np.abs(g.astype(np.int32) - w_.astype(np.int32))
@@ -283,7 +353,7 @@ def _run_walk(hip, seed, ops, tmp_path, oracle_on, nodes, kinds=KINDS):
                 for name in [n for n in ("options", "shard") if n in rigs]:
                     equal(f"{name} against the default renderer", oid, fmt, outs[name][oid].download(), a)
                 if oid in op["settled"]:
-                    got = _fresh_render(hip, last_update[oid], registered, frames, op, nodes)
+                    got = _fresh_render(hip, last_update[oid], registered, frames, op, nodes, mode, wrap)
                     equal("the long-lived default renderer against a brand-new one", oid, fmt, a, got)
                     fresh_checks += 1
                     after_sibling_checks += bool(ops[k - 1].get("only_moves_a_sibling"))
@@ -293,6 +363,9 @@ def _run_walk(hip, seed, ops, tmp_path, oracle_on, nodes, kinds=KINDS):
         if "lanes" in rigs:
             rigs["lanes"].r.sync()
         flush(0)
+        if stats is not None and "plain" in rigs:
+            stats["launches"] = rigs["plain"].ctx.kernel_launches()
+            stats["caller_memory"] = len(rigs["plain"].caller_memory)
     finally:
         for r in rigs.values():
             r.close()
@@ -310,6 +383,30 @@ def test_a_walk_of_scene_updates_renders_the_oracle_picture_in_every_configurati
     assert fresh >= 2
     for p, s in shares.items():
         assert s >= 0.99, f"seed {seed} plane {p}: only {s:.5f} of the bytes identical to the oracle's"
+
+
+@pytest.mark.parametrize("seed", SW.FORMAT_SEEDS)
+def test_a_walk_of_input_formats_matrices_and_alpha_renders_the_oracle_picture_in_every_configuration(hip, seed, tmp_path):
+    """tests/scene_walk.walk_formats: every base format, the three matrices, odd sizes, alpha over other inputs, a sixth of the frames in caller
+    memory; odd seeds in MODE_CPU_OPTIMIZED.  The same four rigs, three comparisons and bars as the first walk."""
+    mode = hip.MODE_CPU_OPTIMIZED if SW.format_mode(seed) == "cpu_optimized" else hip.MODE_GPU_OPTIMIZED
+    stats = {}
+    pools, worst, fresh, _ = _run_walk(hip, seed, SW.walk_formats(seed), tmp_path, oracle_on=True, nodes=False, mode=mode, wrap=True, stats=stats)
+    shares = {p: same / max(total, 1) for p, (same, total) in pools.items()}
+    ran = {k: n for k, n in stats["launches"].items() if n}
+    print(f"format walk {seed} ({SW.format_mode(seed)}): identical to the oracle Y {shares['Y']:.6f} U {shares['U']:.6f} V {shares['V']:.6f} "
+          f"({pools['Y'][1]} / {pools['U'][1]} / {pools['V'][1]} bytes), worst {worst} LSB, {fresh} frames against a new renderer, "
+          f"{stats['caller_memory']} frames in caller memory, launches {ran}")
+    assert worst <= 1
+    assert fresh >= 2
+    for p, s in shares.items():
+        assert s >= 0.99, f"seed {seed} plane {p}: only {s:.5f} of the bytes identical to the oracle's"
+    # what follows from the walk alone (tests/test_scene_walk.py: every seed shows a frame the 4:2:0 block converter does not take)
+    assert stats["launches"]["frame_to_rgba"] - stats["launches"]["frame_to_rgba_420"] > 0, ran
+    if mode == hip.MODE_GPU_OPTIMIZED:
+        assert stats["launches"]["compose_output"] > 0, ran
+    if _torch() is not None:
+        assert stats["caller_memory"] > 0
 
 
 @pytest.mark.parametrize("seed", SW.NODE_SEEDS)
