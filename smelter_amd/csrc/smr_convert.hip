@@ -13,15 +13,43 @@
 #include "smr_convert_420.h"
 #include "smr_convert_hi.h"
 #include "smr_convert_hi422.h"
+#include "smr_convert_route.h"
 #include "smr_svg_nodes.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
 
-// kind: 0 planar (3 R8 planes), 1 NV12 (R8 + RG8)
-template <int KIND>
-__global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up, SurfView vp, SurfView dst, int full, u32 matrix) {
+// Four horizontally adjacent RGBA8 pixels x0 .. x0 + 3 of a row of w, `at` = the address of pixel x0: one 16-byte store, or — the group that
+// straddles the row's right edge — the pixels that exist one by one.
+__device__ __forceinline__ void st_px4(u8 *at, const u32 (&px)[4], int x0, int w) {
+    if (x0 + 3 < w) {
+        *(uint4 *)at = make_uint4(px[0], px[1], px[2], px[3]);
+    } else {
+        for (int i = 0; i < 4 && x0 + i < w; i++) ((u32 *)at)[i] = px[i];
+    }
+}
+// bgra_to_rgba.wgsl:24-28 (sample.bgra: [x2, x1, x0, x3]) / argb_to_rgba.wgsl:24-28 (sample.argb: [x3, x0, x1, x2]): byte permutes
+__device__ __forceinline__ u32 swizzle_px(u32 p, bool bgra) {
+    return bgra ? (p & 0xff00ff00u) | ((p & 0xffu) << 16) | ((p >> 16) & 0xffu) : (p >> 24) | (p << 8);
+}
+
+// The luma texel and the chroma sampler of the general planar / semi-planar kernel: 8-bit planes, or planes of 16-bit words that hold a
+// 10-bit code (smr_convert_hi.h: planar 10-bit, code = word & 0x3ff; P010 / P210, code = word >> 6)
+struct Fetch8 {
+    static __device__ __forceinline__ float luma(const SurfView &p, int x, int y) { return (float)p.ptr[(size_t)y * p.pitch + x] / 255.0f; }
+    static __device__ __forceinline__ float chroma(const SurfView &p, int comps, int c, float u, float v) { return sample_plane_bilinear(p, comps, c, u, v); }
+};
+template <bool P010>
+struct FetchHi {
+    static __device__ __forceinline__ float luma(const SurfView &p, int x, int y) { return cvhi_fetch<P010>(p.ptr + (size_t)y * p.pitch, x); }
+    static __device__ __forceinline__ float chroma(const SurfView &p, int comps, int c, float u, float v) { return sample_plane_bilinear_hi<P010>(p, comps, c, u, v); }
+};
+// planar_yuv_to_rgba.wgsl / nv12_to_rgba.wgsl, a fragment per pixel, any geometry — odd sizes, widths below 8, 1x1 with placeholder chroma
+// planes (planes keep a 1x1 placeholder when the logical chroma size is 0: the sampler asks the planes for their size).
+// kind: 0 planar (3 planes), 1 semi-planar (luma + interleaved chroma in `up`)
+template <int KIND, typename FETCH>
+__device__ __forceinline__ void yuv_to_rgba_body(const SurfView &yp, const SurfView &up, const SurfView &vp, const SurfView &dst, int full, u32 matrix) {
     const SmrMatrixCoef C = smr_matrix_coef(matrix);  // (uniform: the frame's smr_color_matrix)
     const int groups = (dst.w + 3) >> 2;
     const int gx = blockIdx.x * BLOCK + threadIdx.x;
@@ -35,14 +63,14 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up,
         int x = x0 + i;
         if (x >= dst.w) { px[i] = 0; continue; }
         float tu = ((float)x + 0.5f) / (float)dst.w;
-        float yy = (float)yp.ptr[(size_t)y * yp.pitch + x] / 255.0f;
+        float yy = FETCH::luma(yp, x, y);
         float uu, vv;
         if (KIND == 0) {
-            uu = sample_plane_bilinear(up, 1, 0, tu, tv);
-            vv = sample_plane_bilinear(vp, 1, 0, tu, tv);
+            uu = FETCH::chroma(up, 1, 0, tu, tv);
+            vv = FETCH::chroma(vp, 1, 0, tu, tv);
         } else {
-            uu = sample_plane_bilinear(up, 2, 0, tu, tv);
-            vv = sample_plane_bilinear(up, 2, 1, tu, tv);
+            uu = FETCH::chroma(up, 2, 0, tu, tv);
+            vv = FETCH::chroma(up, 2, 1, tu, tv);
         }
         px[i] = yuv_to_rgb_px(yy, uu, vv, full != 0, C);
     }
@@ -53,41 +81,14 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up,
         for (int i = 0; i < 4 && x0 + i < dst.w; i++) *(u32 *)(row + (size_t)(x0 + i) * 4) = px[i];
     }
 }
-
-// The 10-bit twin (smr_convert_hi.h), statement for statement with the 16-bit fetch: any geometry — odd sizes, widths below 8, 1x1 with
-// placeholder chroma planes.  kind: 0 planar 10-bit (3 R16 planes, code = word & 0x3ff), 1 P010 (R16 + RG16, code = word >> 6); limited range.
+template <int KIND>
+__global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba(SurfView yp, SurfView up, SurfView vp, SurfView dst, int full, u32 matrix) {
+    yuv_to_rgba_body<KIND, Fetch8>(yp, up, vp, dst, full, matrix);
+}
+// the 10-bit twin: kind 0 planar 10-bit 4:2:0 / 4:2:2, 1 P010 / P210; limited range
 template <int KIND>
 __global__ __launch_bounds__(BLOCK) void k_yuv_hi_to_rgba(SurfView yp, SurfView up, SurfView vp, SurfView dst, u32 matrix) {
-    const SmrMatrixCoef C = smr_matrix_coef(matrix);
-    const int groups = (dst.w + 3) >> 2;
-    const int gx = blockIdx.x * BLOCK + threadIdx.x;
-    const int y = blockIdx.y;
-    if (gx >= groups) return;
-    const int x0 = gx * 4;
-    const float tv = ((float)y + 0.5f) / (float)dst.h;
-    u32 px[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        int x = x0 + i;
-        if (x >= dst.w) { px[i] = 0; continue; }
-        float tu = ((float)x + 0.5f) / (float)dst.w;
-        float yy = cvhi_fetch<KIND == 1>(yp.ptr + (size_t)y * yp.pitch, x);
-        float uu, vv;
-        if (KIND == 0) {
-            uu = sample_plane_bilinear_hi<false>(up, 1, 0, tu, tv);
-            vv = sample_plane_bilinear_hi<false>(vp, 1, 0, tu, tv);
-        } else {
-            uu = sample_plane_bilinear_hi<true>(up, 2, 0, tu, tv);
-            vv = sample_plane_bilinear_hi<true>(up, 2, 1, tu, tv);
-        }
-        px[i] = yuv_to_rgb_px(yy, uu, vv, false, C);
-    }
-    u8 *row = dst.ptr + (size_t)y * dst.pitch;
-    if (x0 + 3 < dst.w) {
-        *(uint4 *)(row + (size_t)x0 * 4) = make_uint4(px[0], px[1], px[2], px[3]);
-    } else {
-        for (int i = 0; i < 4 && x0 + i < dst.w; i++) *(u32 *)(row + (size_t)(x0 + i) * 4) = px[i];
-    }
+    yuv_to_rgba_body<KIND, FetchHi<KIND == 1>>(yp, up, vp, dst, 0, matrix);
 }
 
 // 10-bit 4:2:2, any geometry.  Planar 10-bit and P210 frames take k_yuv_hi_to_rgba above: its sampler asks the planes for their size, and a
@@ -135,12 +136,8 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba_batch(const ConvBatch B) 
                 for (int i = 0; i < 4; i++) t[i] = 4 * g + i < w ? ((const u32 *)sr)[i] : 0u;
             }
 #pragma unroll
-            for (int i = 0; i < 4; i++) t[i] = J.packed == 3 ? (t[i] & 0xff00ff00u) | ((t[i] & 0xffu) << 16) | ((t[i] >> 16) & 0xffu) : (t[i] >> 24) | (t[i] << 8);
-            if (4 * g + 3 < w) {
-                *(uint4 *)row = make_uint4(t[0], t[1], t[2], t[3]);
-            } else {
-                for (int i = 0; i < 4 && 4 * g + i < w; i++) ((u32 *)row)[i] = t[i];
-            }
+            for (int i = 0; i < 4; i++) t[i] = swizzle_px(t[i], J.packed == 3);
+            st_px4(row, t, 4 * g, w);
         }
         return;
     }
@@ -162,12 +159,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba_batch(const ConvBatch B) 
                 const u32 yb = J.packed == 1 ? ((i & 1) ? c3 : c1) : ((i & 1) ? c2 : c0);
                 px[i] = yuv_to_rgb_px_cr(unorm_of_byte(yb), unorm_of_byte(ub), unorm_of_byte(vb), false, C);
             }
-            u8 *row = J.dst.ptr + ((u32)y * J.dst.pitch + 16u * (u32)g);
-            if (4 * g + 3 < w) {
-                *(uint4 *)row = make_uint4(px[0], px[1], px[2], px[3]);
-            } else {
-                for (int i = 0; i < 4 && 4 * g + i < w; i++) ((u32 *)row)[i] = px[i];
-            }
+            st_px4(J.dst.ptr + ((u32)y * J.dst.pitch + 16u * (u32)g), px, 4 * g, w);
         }
         return;
     }
@@ -251,12 +243,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv_to_rgba_batch(const ConvBatch B) 
             if (!J.sy) { uu = H[0][r][i]; vv = H[1][r][i]; }
             px[i] = yuv_to_rgb_px_cr(yy, uu, vv, J.full != 0, C);
         }
-        u8 *row = J.dst.ptr + ((u32)y * J.dst.pitch + 16u * (u32)g);
-        if (4 * g + 3 < w) {
-            *(uint4 *)row = make_uint4(px[0], px[1], px[2], px[3]);
-        } else {
-            for (int i = 0; i < 4 && 4 * g + i < w; i++) ((u32 *)row)[i] = px[i];
-        }
+        st_px4(J.dst.ptr + ((u32)y * J.dst.pitch + 16u * (u32)g), px, 4 * g, w);
     }
 }
 
@@ -290,23 +277,20 @@ __global__ __launch_bounds__(BLOCK) void k_swizzle(SurfView src, SurfView dst, i
     const int x0 = gx * 4;
     const u8 *srow = src.ptr + (size_t)y * src.pitch;
     u8 *drow = dst.ptr + (size_t)y * dst.pitch;
-    u32 in[4], o[4];
+    u32 t[4];
     if (x0 + 3 < dst.w) {
         uint4 v = *(const uint4 *)(srow + (size_t)x0 * 4);
-        in[0] = v.x; in[1] = v.y; in[2] = v.z; in[3] = v.w;
+        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
     } else {
-        for (int i = 0; i < 4; i++) in[i] = (x0 + i < dst.w) ? *(const u32 *)(srow + (size_t)(x0 + i) * 4) : 0;
+        for (int i = 0; i < 4; i++) t[i] = (x0 + i < dst.w) ? *(const u32 *)(srow + (size_t)(x0 + i) * 4) : 0;
     }
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        u32 p = in[i];
-        if (kind == 0) o[i] = (p & 0xff00ff00u) | ((p & 0xff) << 16) | ((p >> 16) & 0xff);  // [x2,x1,x0,x3]
-        else o[i] = (p >> 24) | (p << 8);                                                    // [x3,x0,x1,x2]
-    }
+    for (int i = 0; i < 4; i++) t[i] = swizzle_px(t[i], kind == 0);
+    // (not st_px4: through it this kernel and the general Y'CbCr ones grow by 15 - 19 instructions)
     if (x0 + 3 < dst.w) {
-        *(uint4 *)(drow + (size_t)x0 * 4) = make_uint4(o[0], o[1], o[2], o[3]);
+        *(uint4 *)(drow + (size_t)x0 * 4) = make_uint4(t[0], t[1], t[2], t[3]);
     } else {
-        for (int i = 0; i < 4 && x0 + i < dst.w; i++) *(u32 *)(drow + (size_t)(x0 + i) * 4) = o[i];
+        for (int i = 0; i < 4 && x0 + i < dst.w; i++) *(u32 *)(drow + (size_t)(x0 + i) * 4) = t[i];
     }
 }
 
@@ -394,75 +378,57 @@ extern "C" __attribute__((visibility("default"))) int smr_debug_convert_stamps(u
 }
 #endif
 
-// MATRIX: the smr_color_matrix of every job of the launch (the host queues per matrix) — a compile-time property, so that the BT.709 launch is
-// the code it was before the matrices and the others are the same instruction stream with four other literals.
-template <bool NV, int MATRIX = SMR_MATRIX_BT709>
+// The body of k_yuv420_to_rgba and k_yuv420_to_rgba_tight.  NV: NV12 | TIGHT: cv420_load_chroma's build that requests nothing behind a window's
+// last column | MATRIX: the smr_color_matrix of every job of the launch (the host queues per matrix) — a compile-time property, so that the
+// BT.709 launch is the code it was before the matrices and the others are the same instruction stream with four other literals.
+// (A macro, not a function: through a function the plain kernel's register allocation moved.)
+#ifdef CV_TIMING
+#define CV_TIMING_ONLY(...) __VA_ARGS__
+#else
+#define CV_TIMING_ONLY(...)
+#endif
+#ifdef SMR_PRIO_CONVERT
+#define CV_SET_PRIO() __builtin_amdgcn_s_setprio(SMR_PRIO_CONVERT)
+#else
+#define CV_SET_PRIO() do { } while (0)
+#endif
+#define YUV420_TO_RGBA_BODY(NV, TIGHT, MATRIX)                                                                                                     \
+    __shared__ float s_ylut[256], s_nlut[256];                                                                                                     \
+    CV_SET_PRIO();                                                                                                                                 \
+    unsigned long long *st = nullptr;                                                                                                              \
+    CV_TIMING_ONLY(st = g_cv_stamps[(blockIdx.x * 4u + (threadIdx.x >> 6)) & 32767u];                                                              \
+                   if ((threadIdx.x & 63) == 0) { st[7] = __builtin_amdgcn_s_memrealtime(); st[1] = st[2] = st[3] = st[4] = st[5] = st[6] = 0; })  \
+    CV_STAMP(st, 0, "s_nop 0");                                                                                                                    \
+    const u32 lane = threadIdx.x & 63u;                                                                                                            \
+    /* both ranges' luma tables: a wave's share may touch several jobs (the full-range luma value of a byte is byte / 255 itself: s_nlut) */      \
+    s_ylut[threadIdx.x & 255] = cv420_luma_of_byte(threadIdx.x & 255u, false);                                                                     \
+    s_nlut[threadIdx.x & 255] = unorm_of_byte(threadIdx.x & 255u);                                                                                 \
+    __syncthreads();                                                                                                                               \
+    CV_STAMP(st, 1, "s_nop 0");                                                                                                                    \
+    cv420_share<NV, TIGHT, MATRIX>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, lane, s_ylut, s_nlut, st);                              \
+    CV_TIMING_ONLY(st = g_cv_stamps[(blockIdx.x * 4u + (threadIdx.x >> 6)) & 32767u];)                                                             \
+    CV_STAMP(st, 5, "s_nop 0");            /* the queue is dry, the last stores are issued */                                                      \
+    CV_STAMP(st, 6, "s_waitcnt vmcnt(0)"); /* ... and acknowledged */                                                                              \
+    CV_TIMING_ONLY(if ((threadIdx.x & 63) == 0) {                                                                                                  \
+        st[8] = __builtin_amdgcn_s_memrealtime();                                                                                                  \
+        unsigned xcc, hw;                                                                                                                          \
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));                                                                         \
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                                                                           \
+        st[9] = ((unsigned long long)xcc << 32) | hw;                                                                                              \
+    })
+
 #ifndef SMR_CONVERT_MIN_WAVES
 #define SMR_CONVERT_MIN_WAVES 1  // waves per SIMD the converter's register allocation must leave room for (A/B knob: 8 = at most 64 registers, so that more of its waves fit beside another lane's resampler)
 #endif
-__global__ __launch_bounds__(BLOCK, SMR_CONVERT_MIN_WAVES) void k_yuv420_to_rgba(const ConvBatch B) {
-    __shared__ float s_ylut[256], s_nlut[256];
-#ifdef SMR_PRIO_CONVERT
-    __builtin_amdgcn_s_setprio(SMR_PRIO_CONVERT);
-#endif
-#ifdef CV_TIMING
-    unsigned long long *st = g_cv_stamps[(blockIdx.x * 4u + (threadIdx.x >> 6)) & 32767u];
-    if ((threadIdx.x & 63) == 0) { st[7] = __builtin_amdgcn_s_memrealtime(); st[1] = st[2] = st[3] = st[4] = st[5] = st[6] = 0; }
-    CV_STAMP(st, 0, "s_nop 0");
-#else
-    unsigned long long *st = nullptr;
-#endif
-    const u32 lane = threadIdx.x & 63u;
-    // both ranges' luma tables: a wave's share may touch several jobs (the full-range luma value of a byte is byte / 255 itself: s_nlut)
-    s_ylut[threadIdx.x & 255] = cv420_luma_of_byte(threadIdx.x & 255u, false);
-    s_nlut[threadIdx.x & 255] = unorm_of_byte(threadIdx.x & 255u);
-    __syncthreads();
-    CV_STAMP(st, 1, "s_nop 0");
-    cv420_share<NV, false, MATRIX>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, lane, s_ylut, s_nlut, st);
-#ifdef CV_TIMING
-    st = g_cv_stamps[(blockIdx.x * 4u + (threadIdx.x >> 6)) & 32767u];
-#endif
-    CV_STAMP(st, 5, "s_nop 0");                // the queue is dry, the last stores are issued
-    CV_STAMP(st, 6, "s_waitcnt vmcnt(0)");     // ... and acknowledged
-#ifdef CV_TIMING
-    if ((threadIdx.x & 63) == 0) { st[8] = __builtin_amdgcn_s_memrealtime(); unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); st[9] = ((unsigned long long)xcc << 32) | hw; }
-#endif
-}
-
-// The same for frames with a chroma plane whose rows fill its pitch and that the library did not allocate (conv_420_ok: a wrapped decoder
-// surface with tight rows): cv420_load_chroma's TIGHT build requests nothing behind a window's last column.  A kernel of its own, so that the
-// plain one stays the instruction stream it was measured as.
 template <bool NV, int MATRIX = SMR_MATRIX_BT709>
-__global__ __launch_bounds__(BLOCK) void k_yuv420_to_rgba_tight(const ConvBatch B) {
-    __shared__ float s_ylut[256], s_nlut[256];
-#ifdef SMR_PRIO_CONVERT
-    __builtin_amdgcn_s_setprio(SMR_PRIO_CONVERT);
-#endif
-#ifdef CV_TIMING
-    unsigned long long *st = g_cv_stamps[(blockIdx.x * 4u + (threadIdx.x >> 6)) & 32767u];
-    if ((threadIdx.x & 63) == 0) { st[7] = __builtin_amdgcn_s_memrealtime(); st[1] = st[2] = st[3] = st[4] = st[5] = st[6] = 0; }
-    CV_STAMP(st, 0, "s_nop 0");
-#else
-    unsigned long long *st = nullptr;
-#endif
-    const u32 lane = threadIdx.x & 63u;
-    // both ranges' luma tables: a wave's share may touch several jobs (the full-range luma value of a byte is byte / 255 itself: s_nlut)
-    s_ylut[threadIdx.x & 255] = cv420_luma_of_byte(threadIdx.x & 255u, false);
-    s_nlut[threadIdx.x & 255] = unorm_of_byte(threadIdx.x & 255u);
-    __syncthreads();
-    CV_STAMP(st, 1, "s_nop 0");
-    cv420_share<NV, true, MATRIX>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, lane, s_ylut, s_nlut, st);
-#ifdef CV_TIMING
-    st = g_cv_stamps[(blockIdx.x * 4u + (threadIdx.x >> 6)) & 32767u];
-#endif
-    CV_STAMP(st, 5, "s_nop 0");                // the queue is dry, the last stores are issued
-    CV_STAMP(st, 6, "s_waitcnt vmcnt(0)");     // ... and acknowledged
-#ifdef CV_TIMING
-    if ((threadIdx.x & 63) == 0) { st[8] = __builtin_amdgcn_s_memrealtime(); unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); st[9] = ((unsigned long long)xcc << 32) | hw; }
-#endif
-}
+__global__ __launch_bounds__(BLOCK, SMR_CONVERT_MIN_WAVES) void k_yuv420_to_rgba(const ConvBatch B) { YUV420_TO_RGBA_BODY(NV, false, MATRIX) }
 
-// 10-bit 4:2:0 frames the block converter takes (smr_convert_hi.h, conv_hi_mode): the same persistent launch cut into equal shares, with two
+// The same for frames with a chroma plane the library did not allocate (smr_convert_route.h: a wrapped decoder surface, tight rows or wide
+// ones).  A kernel of its own — and its own launch bounds — so that the plain one stays the instruction stream it was measured as.
+template <bool NV, int MATRIX = SMR_MATRIX_BT709>
+__global__ __launch_bounds__(BLOCK) void k_yuv420_to_rgba_tight(const ConvBatch B) { YUV420_TO_RGBA_BODY(NV, true, MATRIX) }
+
+// 10-bit 4:2:0 frames the block converter takes (smr_convert_hi.h, conv_route): the same persistent launch cut into equal shares, with two
 // 1024-entry tables (the code's unorm value, its luma range expansion) built per workgroup with the operations themselves — 8 KB of LDS, the four
 // workgroups a CU is given (83 / 84 registers: DESIGN.md 3l) stay far below its 160 KB.  One kernel per format, no plain / tight pair: no load leaves a plane row's bytes.
 template <bool P010>
@@ -473,7 +439,7 @@ __global__ __launch_bounds__(BLOCK) void k_yuv420_hi_to_rgba(const ConvBatch B) 
     cvhi_share<P010>(B, blockIdx.x, cv_uniform(threadIdx.x >> 6), gridDim.x, threadIdx.x & 63u, s_ylut, s_ulut);
 }
 
-// 10-bit 4:2:2 frames the block converter takes (smr_convert_hi422.h, conv_hi422_mode): the launch above with the 4:2:2 fetch — planar 10-bit,
+// 10-bit 4:2:2 frames the block converter takes (smr_convert_hi422.h, conv_route): the launch above with the 4:2:2 fetch — planar 10-bit,
 // P210 (a chroma row per luma row) or v210 (16 bytes of the row per thread, the fields chosen by g % 3).  The same two tables.
 template <int LAYOUT>
 __global__ __launch_bounds__(BLOCK) void k_yuv422_hi_to_rgba(const ConvBatch B) {
@@ -576,98 +542,101 @@ u32 host_unorm8(float x) {
 
 }  // namespace
 
-
 static int smr_frame_to_rgba_general(smr_ctx *ctx, const smr_frame *in, smr_surface *node);  // one launch per frame, any geometry
 
-// k_yuv_to_rgba_batch's frames: planar 4:2:0 / 4:2:2 / 4:4:4 and NV12 whose subsampled axes are even (chroma planes exactly half), within the
-// size the coordinate argument holds for
-static bool conv_batchable(const smr_ctx *ctx, const smr_frame *in) {
-    const u32 fmt = frame_base_format(in->format);  // (the colour matrix changes no route)
-    if (in->width < 2 || in->height < 2 || in->width > 16384 || in->height > 16384 || ctx->convert_impl == SMR_CONVERT_GENERAL) return false;
-    if (fmt == SMR_FRAME_UYVY422 || fmt == SMR_FRAME_YUYV422)
-        return in->width % 2 == 0 && in->width >= 8 && in->planes[0] && (in->planes[0]->pitch & 3u) == 0 && (((uintptr_t)in->planes[0]->ptr) & 3) == 0;
-    if (fmt == SMR_FRAME_BGRA || fmt == SMR_FRAME_ARGB)
-        return in->planes[0] && (in->planes[0]->pitch & 15u) == 0 && (((uintptr_t)in->planes[0]->ptr) & 15) == 0;
-    const bool nv = fmt == SMR_FRAME_NV12;
-    const bool sx = fmt != SMR_FRAME_PLANAR_YUV444, sy = fmt == SMR_FRAME_PLANAR_YUV420 || fmt == SMR_FRAME_PLANAR_YUVJ420 || nv;
-    if (fmt > SMR_FRAME_PLANAR_YUVJ420 && !nv) return false;  // (BGRA / ARGB / RGBA: byte permutes of their own)
-    if ((sx && in->width % 2) || (sy && in->height % 2)) return false;
-    return in->planes[0] && in->planes[1] && (nv || in->planes[2]);
+bool smr_conv_rgb12_ok(const smr_ctx *ctx, const smr_frame *in) { return conv_rgb12_ok(ctx, in); }
+
+// Per route (smr_convert_route.h): the kernel a queue of jobs is launched with and how its grid is sized.
+enum ConvGrid {
+    GRID_4X2,          // k_yuv_to_rgba_batch: a thread per 4 x 2 pixels of the largest frame, a grid layer per job
+    // the persistent block converters — as many workgroups as stay resident together, never more waves than units:
+    WG_BY_UNITS,       // the 8-bit kernels (6 per CU fit at 77 registers).  convert_wg_per_cu 0 (the default): five per CU for a batch of a few frames,
+                       // six for a large one.  With two frames in flight the kernel runs beside the other lane's kernels; configs[2] (8 640 units: 1.4
+                       // per wave at six) gains 2 % at five, configs[3] (64 800 units) loses 1 % (profiles/r06_sensitivity.txt section 9).  A dynamic LDS
+                       // request that caps a CU at exactly that number (an even spread: every SIMD the same number of waves) was measured and is no
+                       // faster in the kernel trace (6 per CU: 23.1 us capped, 22.0 us uncapped, 4 per CU: 23.3 / 23.7 —
+                       // profiles/r05_convert_waves.txt) while it keeps other launches' workgroups off the CU; the knob remains for laboratory
+                       // builds (SMR_CONVERT_LDS_PAD)
+    WG_FOUR,           // the 4:2:0 10-bit kernels: four workgroups per CU, the number they were measured at when they held 101 registers
+                       // and a fifth could only queue; with the matrix coefficients in scalar registers they hold 83 / 84 and a fifth would fit
+                       //  — kept at four until a fifth is measured: not on the benchmark's path
+    WG_RESIDENT        // the 4:2:2 kernels: as many workgroups per CU as the kernel's own registers and LDS keep resident (asked once per context and
+                       // route: these kernels read the matrix from the job, one instantiation per route), six at the most
+};
+struct ConvKernel {
+    ConvRoute route;
+    void (*kernel)(const ConvBatch);
+    ConvGrid grid;
+};
+static constexpr ConvKernel conv_kernels[CONV_ROUTES] = {
+    {CONV_BATCH_4X2, k_yuv_to_rgba_batch, GRID_4X2},
+    {CONV_420_PLANAR, k_yuv420_to_rgba<false, SMR_MATRIX_BT709>, WG_BY_UNITS},
+    {CONV_420_NV12, k_yuv420_to_rgba<true, SMR_MATRIX_BT709>, WG_BY_UNITS},
+    {CONV_420_PLANAR_TIGHT, k_yuv420_to_rgba_tight<false, SMR_MATRIX_BT709>, WG_BY_UNITS},
+    {CONV_420_NV12_TIGHT, k_yuv420_to_rgba_tight<true, SMR_MATRIX_BT709>, WG_BY_UNITS},
+    {CONV_HI420_PLANAR, k_yuv420_hi_to_rgba<false>, WG_FOUR},
+    {CONV_HI420_P010, k_yuv420_hi_to_rgba<true>, WG_FOUR},
+    {CONV_HI422_PLANAR, k_yuv422_hi_to_rgba<CV422_PLANAR>, WG_RESIDENT},
+    {CONV_HI422_P210, k_yuv422_hi_to_rgba<CV422_P210>, WG_RESIDENT},
+    {CONV_HI422_V210, k_yuv422_hi_to_rgba<CV422_V210>, WG_RESIDENT},
+    {CONV_420_PLANAR_601, k_yuv420_to_rgba<false, SMR_MATRIX_BT601>, WG_BY_UNITS},
+    {CONV_420_NV12_601, k_yuv420_to_rgba<true, SMR_MATRIX_BT601>, WG_BY_UNITS},
+    {CONV_420_PLANAR_TIGHT_601, k_yuv420_to_rgba_tight<false, SMR_MATRIX_BT601>, WG_BY_UNITS},
+    {CONV_420_NV12_TIGHT_601, k_yuv420_to_rgba_tight<true, SMR_MATRIX_BT601>, WG_BY_UNITS},
+    {CONV_420_PLANAR_2020, k_yuv420_to_rgba<false, SMR_MATRIX_BT2020_NCL>, WG_BY_UNITS},
+    {CONV_420_NV12_2020, k_yuv420_to_rgba<true, SMR_MATRIX_BT2020_NCL>, WG_BY_UNITS},
+    {CONV_420_PLANAR_TIGHT_2020, k_yuv420_to_rgba_tight<false, SMR_MATRIX_BT2020_NCL>, WG_BY_UNITS},
+    {CONV_420_NV12_TIGHT_2020, k_yuv420_to_rgba_tight<true, SMR_MATRIX_BT2020_NCL>, WG_BY_UNITS},
+};
+constexpr bool conv_kernels_in_route_order() {
+    for (int r = 0; r < CONV_ROUTES; r++)
+        if (conv_kernels[r].route != r) return false;
+    return true;
+}
+static_assert(conv_kernels_in_route_order() && CONV_ROUTES <= 24, "conv_kernels[r] must be the kernel of route r; smr_ctx::convert_resident holds a slot per route");
+
+// Launches the jobs queued for route r (none: nothing happens) and empties the queue.
+struct ConvQueue {
+    ConvBatch B;
+    u32 nb = 0;
+    int mw = 0, mh = 0;
+};
+static int conv_flush(smr_ctx *ctx, int r, ConvQueue &Q) {
+    if (!Q.nb) return SMR_OK;
+    const ConvKernel &K = conv_kernels[r];
+    StageScope scope(ctx, SMR_STAGE_INGEST);
+    ctx->kernel_launches[SMR_KERNEL_FRAME_TO_RGBA]++;  // (per launch)
+    if (K.grid == GRID_4X2) {
+        hipLaunchKernelGGL(K.kernel, dim3((unsigned)((Q.mw + 255) / 256), (unsigned)((Q.mh + 7) / 8), Q.nb), dim3(BLOCK), 0, ctx->stream, Q.B);
+    } else {
+        ctx->kernel_launches[SMR_KERNEL_FRAME_TO_RGBA_420]++;
+        u32 total = 0;
+        for (u32 j = 0; j < Q.nb; j++) total += (((u32)Q.B.j[j].dst.w + 255u) / 256u) * (((u32)Q.B.j[j].dst.h + 3u) / 4u);
+        int per_cu = 4;
+        if (K.grid == WG_BY_UNITS) per_cu = ctx->convert_wg_per_cu > 0 ? ctx->convert_wg_per_cu : (total >= 32768u ? 6 : 5);
+        if (K.grid == WG_RESIDENT) {
+            int &resident = ctx->convert_resident[r];
+            if (!resident) {
+                SMR_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, K.kernel, BLOCK, 0));
+                if (resident < 1) resident = 1;
+            }
+            per_cu = resident;
+        }
+        u32 blocks = (u32)ctx->cu_count * (u32)(per_cu > 6 ? 6 : per_cu);
+        if (blocks > (total + 3u) / 4u) blocks = (total + 3u) / 4u;
+        // the partition (smr_convert_batch.h): bands of block rows dealt to the XCDs, equal shares per wave inside an XCD
+        const u32 bands = cv_plan(Q.B, (int)Q.nb);
+        if (blocks < (bands < 8u ? bands : 8u)) blocks = bands < 8u ? bands : 8u;  // (every XCD that owns a band runs a workgroup)
+        hipLaunchKernelGGL(K.kernel, dim3(blocks), dim3(BLOCK), K.grid == WG_BY_UNITS ? ctx->convert_lds_pad : 0u, ctx->stream, Q.B);
+    }
+    Q.nb = 0; Q.mw = 0; Q.mh = 0;
+    SMR_HIP(ctx, hipGetLastError());
+    return SMR_OK;
 }
 
-// k_yuv420_to_rgba's frames (cv420_block, smr_convert_420.h): 4:2:0 planar / NV12, width a multiple of 4 from 8, even height, every plane
-// dword-aligned.  The plain kernel reads up to a dword past the last block's window; the bytes of that dword are never used (the window's
-// last column is the plane's edge, repeated), but they are read: a plane the library allocated may be read past a row's end — the next row,
-// or the 16 bytes every allocation ends with (SMR_SURFACE_TAIL) — a wrapped one is read inside its rows' bytes only: it takes
-// k_yuv420_to_rgba_tight, which requests nothing behind a window's last column (tight rows — a decoder's pitch == bytes per row — or wide ones).  -> 0: not a frame for the block converter | 1: the plain kernel | 2: the tight one
-static int conv_420_mode(const smr_ctx *ctx, const smr_frame *in) {
-    const u32 fmt = frame_base_format(in->format);  // (the colour matrix changes no route)
-    if (ctx->convert_impl != SMR_CONVERT_AUTO) return 0;
-    const bool nv = fmt == SMR_FRAME_NV12;
-    if (fmt != SMR_FRAME_PLANAR_YUV420 && fmt != SMR_FRAME_PLANAR_YUVJ420 && !nv) return 0;
-    if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return 0;
-    auto dwords = [](const smr_surface *s) { return s && (s->pitch & 3u) == 0 && (((uintptr_t)s->ptr) & 3) == 0; };
-    if (!dwords(in->planes[0]) || !dwords(in->planes[1]) || (!nv && !dwords(in->planes[2]))) return 0;
-    const u32 cw = in->width / 2;
-    // the last block's window starts at chroma column cw - 3: its bytes begin in the dword at ((cw - 3) [* 2]) & ~3 and the loads reach 8 (12) bytes from there
-    const u32 need = nv ? ((2u * (cw - 3u)) & ~3u) + 12u : ((cw - 3u) & ~3u) + 8u;
-    const u32 row = nv ? 2u * cw : cw;
-    if (in->planes[0]->pitch < in->width || in->planes[1]->pitch < row || (!nv && in->planes[2]->pitch < row)) return 0;
-    // (a wrapped plane with a wide pitch still ends with its last ROW for many producers — pitch * (h - 1) + row bytes, not pitch * h — and the plain
-    //  kernel's reach into that row's padding would leave the allocation: every plane the library does not own takes the tight kernel, + 2 %)
-    (void)need;
-    auto reach_ok = [&](const smr_surface *s) { return s->owned; };
-    return reach_ok(in->planes[1]) && (nv || reach_ok(in->planes[2])) ? 1 : 2;
-}
-static bool conv_420_ok(const smr_ctx *ctx, const smr_frame *in) { return conv_420_mode(ctx, in) != 0; }
-
-// k_yuv420_hi_to_rgba's frames (smr_convert_hi.h): P010 / planar 10-bit, width a multiple of 4 from 8, even height.  A luma row of a block is
-// one 8-byte load at 8 g: the Y plane's pointer and pitch are 8-byte aligned; the chroma loads are dwords: dword-aligned.  Nothing else: the
-// kernel requests no byte outside a row's own bytes, so owned and wrapped planes, wide and tight rows are one case.
-static bool conv_hi_mode(const smr_ctx *ctx, const smr_frame *in) {
-    const u32 fmt = frame_base_format(in->format);  // (the colour matrix changes no route)
-    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth(fmt) || frame_format_is_hi_depth_422(fmt)) return false;
-    const bool nv = fmt == SMR_FRAME_P010;
-    if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return false;
-    auto aligned = [](const smr_surface *s, uintptr_t a) { return s && (s->pitch & (a - 1)) == 0 && (((uintptr_t)s->ptr) & (a - 1)) == 0; };
-    if (!aligned(in->planes[0], 8) || !aligned(in->planes[1], 4) || (!nv && !aligned(in->planes[2], 4))) return false;
-    const u32 crow = nv ? 2u * in->width : in->width;  // bytes of a chroma row: w / 2 columns of 4 (2) bytes
-    return in->planes[0]->pitch >= 2u * in->width && in->planes[1]->pitch >= crow && (nv || in->planes[2]->pitch >= crow);
-}
-
-// k_yuv422_hi_to_rgba's frames (smr_convert_hi422.h): planar 10-bit 4:2:2, P210, v210; width a multiple of 4 from 8, even height.  A luma row
-// of a block is one 8-byte load at 8 g, a v210 row of a block two 8-byte loads at 32 (g / 3) + 8 (g % 3): the Y plane's (v210: the plane's)
-// pointer and pitch are 8-byte aligned; the chroma loads are dwords: dword-aligned.  Nothing else: the kernel requests no byte outside a row's
-// own bytes, so owned and wrapped planes, wide and tight rows (a capture card's stride among them) are one case.
-static bool conv_hi422_mode(const smr_ctx *ctx, const smr_frame *in) {
-    const u32 fmt = frame_base_format(in->format);  // (the colour matrix changes no route)
-    if (ctx->convert_impl != SMR_CONVERT_AUTO || !frame_format_is_hi_depth_422(fmt)) return false;
-    if (in->width % 4 || in->width < 8 || in->height % 2 || in->height < 2 || in->width > 16384 || in->height > 16384) return false;
-    auto aligned = [](const smr_surface *s, uintptr_t a) { return s && (s->pitch & (a - 1)) == 0 && (((uintptr_t)s->ptr) & (a - 1)) == 0; };
-    if (!aligned(in->planes[0], 8)) return false;
-    if (fmt == SMR_FRAME_V210) return in->planes[0]->pitch >= 16u * ((in->width + 5u) / 6u);
-    const bool nv = fmt == SMR_FRAME_P210;
-    if (!aligned(in->planes[1], 4) || (!nv && !aligned(in->planes[2], 4))) return false;
-    const u32 crow = nv ? 2u * in->width : in->width;  // bytes of a chroma row: w / 2 columns of 4 (2) bytes
-    return in->planes[0]->pitch >= 2u * in->width && in->planes[1]->pitch >= crow && (nv || in->planes[2]->pitch >= crow);
-}
-
-bool smr_conv_rgb12_ok(const smr_ctx *ctx, const smr_frame *in) {
-    return in && (conv_420_ok(ctx, in) || conv_hi_mode(ctx, in) || conv_hi422_mode(ctx, in)) && 3u * in->width <= 7682u * 2u;
-}
-
-// k_yuv420_to_rgba / _tight of one matrix: kind 1 planar | 2 NV12 | 3 tight planar | 4 tight NV12
-template <int MATRIX>
-static void launch_cv420(int kind, u32 blocks, u32 lds_pad, hipStream_t stream, const ConvBatch &B) {
-    if (kind == 1) hipLaunchKernelGGL((k_yuv420_to_rgba<false, MATRIX>), dim3(blocks), dim3(BLOCK), lds_pad, stream, B);
-    else if (kind == 2) hipLaunchKernelGGL((k_yuv420_to_rgba<true, MATRIX>), dim3(blocks), dim3(BLOCK), lds_pad, stream, B);
-    else if (kind == 3) hipLaunchKernelGGL((k_yuv420_to_rgba_tight<false, MATRIX>), dim3(blocks), dim3(BLOCK), lds_pad, stream, B);
-    else hipLaunchKernelGGL((k_yuv420_to_rgba_tight<true, MATRIX>), dim3(blocks), dim3(BLOCK), lds_pad, stream, B);
-}
-
-// smr_frame_to_rgba for several frames: one launch for every 16 frames of a kind (k_yuv420_to_rgba planar / NV12 — per colour matrix, whose
-// instantiations differ: a batch that mixes matrices makes one launch per matrix present —, the 10-bit block converters, k_yuv_to_rgba_batch),
-// the others one by one.  Everything queued is launched before the call returns, errors included.
+// smr_frame_to_rgba for several frames: one launch for every 16 frames of a route (smr_convert_route.h: k_yuv420_to_rgba planar / NV12 per colour
+// matrix, whose instantiations differ — a batch that mixes matrices makes one launch per matrix present —, the 10-bit block converters,
+// k_yuv_to_rgba_batch), the others one by one.  Everything queued is launched before the call returns, errors included.
 int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surface *const *nodes, u32 n, const u8 *rgb12) {
     if (!ctx || (n && (!in || !nodes))) return SMR_ERR_INVALID;
     // validate first, enqueue afterwards: no frame is left half-queued by a bad one behind it
@@ -675,104 +644,34 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         if (!in[i] || !nodes[i]) return SMR_ERR_INVALID;
         if (rgb12 && rgb12[i]) {
             if (nodes[i]->fmt != SMR_PX_R8 || nodes[i]->w != 3 * in[i]->width || nodes[i]->h != in[i]->height || (nodes[i]->pitch & 3u) || (((uintptr_t)nodes[i]->ptr) & 3) ||
-                !(conv_420_ok(ctx, in[i]) || conv_hi_mode(ctx, in[i]) || conv_hi422_mode(ctx, in[i])))
+                !conv_route_is_block(conv_route(ctx, in[i], true)))
                 return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: an RGB12 node must be R8 %ux%u of a 4:2:0 frame the block converter takes", 3 * in[i]->width, in[i]->height);
         } else if (nodes[i]->fmt != SMR_PX_RGBA8 || nodes[i]->w != in[i]->width || nodes[i]->h != in[i]->height)
             return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: node surface must be RGBA8 %ux%u", in[i]->width, in[i]->height);
         if (int rc = smr_validate_frame(ctx, in[i], "smr_frame_to_rgba")) return rc;
     }
-    struct Queue {
-        ConvBatch B;
-        u32 nb = 0;
-        int mw = 0, mh = 0;
-    };
-    constexpr int NK = 10, NQ = NK + 4 * (SMR_MATRIX_COUNT - 1);
-    // kernel kinds — 0: k_yuv_to_rgba_batch | 1: k_yuv420_to_rgba planar | 2: ... NV12 | 3, 4: k_yuv420_to_rgba_tight planar, NV12 | 5, 6: k_yuv420_hi_to_rgba planar
-    // 10-bit, P010 | 7, 8, 9: k_yuv422_hi_to_rgba planar 10-bit 4:2:2, P210, v210.
-    // Queues — per (kind, matrix) for kinds 1 - 4, whose matrix is a template parameter of the kernel: queue `kind` holds the BT.709 jobs (an
-    // all-709 batch makes the launches it always made), queue NK + 4 (m - 1) + kind - 1 those of matrix m; a batch that mixes matrices makes
-    // one launch per matrix present.  The other kinds read the matrix from the job: one queue each.
-    Queue q[NQ];
-    auto flush = [&](int qi) -> int {
-        Queue &Q = q[qi];
-        if (!Q.nb) return SMR_OK;
-        const int k = qi < NK ? qi : 1 + (qi - NK) % 4, m = qi < NK ? 0 : 1 + (qi - NK) / 4;
-        StageScope scope(ctx, SMR_STAGE_INGEST);
-        ctx->kernel_launches[SMR_KERNEL_FRAME_TO_RGBA]++;  // (per launch)
-        if (k != 0) ctx->kernel_launches[SMR_KERNEL_FRAME_TO_RGBA_420]++;
-        if (k == 0) hipLaunchKernelGGL(k_yuv_to_rgba_batch, dim3((unsigned)((Q.mw + 255) / 256), (unsigned)((Q.mh + 7) / 8), Q.nb), dim3(BLOCK), 0, ctx->stream, Q.B);
-        else {
-            // as many workgroups as stay resident together (6 per CU at 77 registers: convert_wg_per_cu), never more waves than units.  A dynamic LDS
-            // request that caps a CU at exactly that number (an even spread: every SIMD the same number of waves) was measured and is no
-            // faster in the kernel trace (6 per CU: 23.1 us capped, 22.0 us uncapped, 4 per CU: 23.3 / 23.7 — profiles/r05_convert_waves.txt)
-            // while it keeps other launches' workgroups off the CU; the knob remains for laboratory builds (SMR_CONVERT_LDS_PAD)
-            u32 total = 0;
-            for (u32 j = 0; j < Q.nb; j++) total += (((u32)Q.B.j[j].dst.w + 255u) / 256u) * (((u32)Q.B.j[j].dst.h + 3u) / 4u);
-            // convert_wg_per_cu 0 (the default): five per CU for a batch of a few frames, six for a large one.  With two frames in flight the
-            // kernel runs beside the other lane's kernels; configs[2] (8 640 units: 1.4 per wave at six) gains 2 % at five, configs[3]
-            // (64 800 units) loses 1 % (profiles/r06_sensitivity.txt section 9)
-            const int want = ctx->convert_wg_per_cu > 0 ? ctx->convert_wg_per_cu : (total >= 32768u ? 6 : 5);
-            // (the 4:2:0 10-bit kernels: four workgroups per CU, the number they were measured at when they held 101 registers and a
-            //  fifth could only queue; with the matrix coefficients in scalar registers they hold 83 / 84 and a fifth would fit — kept at
-            //  four until a fifth is measured: not on the benchmark's path)
-            u32 per_cu = k >= 5 ? 4u : (u32)(want > 6 ? 6 : want);
-            if (k >= 7) {  // the 4:2:2 kernels: as many workgroups per CU as the kernel's own registers and LDS keep resident (asked once per context)
-                const void *kern = k == 7 ? (const void *)k_yuv422_hi_to_rgba<CV422_PLANAR> : k == 8 ? (const void *)k_yuv422_hi_to_rgba<CV422_P210> : (const void *)k_yuv422_hi_to_rgba<CV422_V210>;
-                int resident = 0;  // (key 2000 + k: one instantiation per kind — these kernels read the matrix from the job, so the key need not tell matrices apart)
-                for (auto &o : ctx->mfma_occupancy)
-                    if (o.kernel == 2000 + k && o.lds == 0) resident = o.per_cu;
-                if (!resident) {
-                    SMR_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, BLOCK, 0));
-                    if (resident < 1) resident = 1;
-                    ctx->mfma_occupancy.push_back({2000 + k, 0, resident});
-                }
-                per_cu = (u32)(resident > 6 ? 6 : resident);
-            }
-            u32 blocks = (u32)ctx->cu_count * per_cu;
-            if (blocks > (total + 3u) / 4u) blocks = (total + 3u) / 4u;
-            // the partition (smr_convert_420.h): bands of block rows dealt to the XCDs, equal shares per wave inside an XCD
-            const u32 bands = cv420_plan(Q.B, (int)Q.nb, blocks * 4u);
-            if (blocks < (bands < 8u ? bands : 8u)) blocks = bands < 8u ? bands : 8u;  // (every XCD that owns a band runs a workgroup)
-            const u32 lds_pad = ctx->convert_lds_pad;
-            if (k <= 4) {
-                if (m == SMR_MATRIX_BT601) launch_cv420<SMR_MATRIX_BT601>(k, blocks, lds_pad, ctx->stream, Q.B);
-                else if (m == SMR_MATRIX_BT2020_NCL) launch_cv420<SMR_MATRIX_BT2020_NCL>(k, blocks, lds_pad, ctx->stream, Q.B);
-                else launch_cv420<SMR_MATRIX_BT709>(k, blocks, lds_pad, ctx->stream, Q.B);
-            }
-            else if (k == 5) hipLaunchKernelGGL(k_yuv420_hi_to_rgba<false>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
-            else if (k == 6) hipLaunchKernelGGL(k_yuv420_hi_to_rgba<true>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
-            else if (k == 7) hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_PLANAR>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
-            else if (k == 8) hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_P210>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
-            else hipLaunchKernelGGL(k_yuv422_hi_to_rgba<CV422_V210>, dim3(blocks), dim3(BLOCK), 0, ctx->stream, Q.B);
-        }
-        Q.nb = 0; Q.mw = 0; Q.mh = 0;
-        SMR_HIP(ctx, hipGetLastError());
-        return SMR_OK;
-    };
+    ConvQueue q[CONV_ROUTES];  // one per route: an all-709 batch makes the launches it always made
     auto flush_all = [&]() -> int {
         int rc = SMR_OK;
-        for (int k = 0; k < NQ; k++)
-            if (int r = flush(k)) rc = rc ? rc : r;
+        for (int r = 0; r < CONV_ROUTES; r++)
+            if (int e = conv_flush(ctx, r, q[r])) rc = rc ? rc : e;
         return rc;
     };
     for (u32 i = 0; i < n; i++) {
         const bool c12 = rgb12 && rgb12[i];
         const u32 fmt = frame_base_format(in[i]->format), matrix = frame_matrix(in[i]->format);
-        const bool aligned16 = c12 || ((((uintptr_t)nodes[i]->ptr) & 15) == 0 && (nodes[i]->pitch & 15u) == 0);  // (the block kernels store 16 B)
-        const bool nv = fmt == SMR_FRAME_NV12 || fmt == SMR_FRAME_P010 || fmt == SMR_FRAME_P210;
-        const int mode = conv_420_mode(ctx, in[i]);
-        const int k = !aligned16 ? -1 : conv_hi422_mode(ctx, in[i]) ? (fmt == SMR_FRAME_V210 ? 9 : nv ? 8 : 7) : conv_hi_mode(ctx, in[i]) ? (nv ? 6 : 5) : mode ? (nv ? 2 : 1) + (mode == 2 ? 2 : 0) : conv_batchable(ctx, in[i]) ? 0 : -1;
-        if (k < 0) {
+        const ConvRoute r = conv_route(ctx, in[i], c12 || ((((uintptr_t)nodes[i]->ptr) & 15) == 0 && (nodes[i]->pitch & 15u) == 0));
+        if (r == CONV_GENERAL) {
             if (int rc = smr_frame_to_rgba_general(ctx, in[i], nodes[i])) {
                 (void)flush_all();
                 return rc;
             }
             continue;
         }
-        const int qi = k >= 1 && k <= 4 && matrix ? NK + 4 * ((int)matrix - 1) + k - 1 : k;
-        Queue &Q = q[qi];
+        ConvQueue &Q = q[r];
         ConvJob &J = Q.B.j[Q.nb++];
         J.matrix = (int)matrix;
+        const bool nv = fmt == SMR_FRAME_NV12 || fmt == SMR_FRAME_P010 || fmt == SMR_FRAME_P210;
         const bool packed = fmt == SMR_FRAME_UYVY422 || fmt == SMR_FRAME_YUYV422 || fmt == SMR_FRAME_BGRA || fmt == SMR_FRAME_ARGB ||
                             fmt == SMR_FRAME_V210;
         J.yp = view_of(in[i]->planes[0]);
@@ -789,7 +688,7 @@ int smr_frames_to_rgba_batch(smr_ctx *ctx, const smr_frame *const *in, smr_surfa
         Q.mw = (int)in[i]->width > Q.mw ? (int)in[i]->width : Q.mw;
         Q.mh = (int)in[i]->height > Q.mh ? (int)in[i]->height : Q.mh;
         if (Q.nb == MAX_CONV_JOBS)
-            if (int rc = flush(qi)) {
+            if (int rc = conv_flush(ctx, r, Q)) {
                 (void)flush_all();
                 return rc;
             }
@@ -813,48 +712,21 @@ static int smr_frame_to_rgba_general(smr_ctx *ctx, const smr_frame *in, smr_surf
     SurfView dst = view_of(node);
     const int w = (int)in->width, h = (int)in->height;
     const u32 fmt = frame_base_format(in->format), matrix = frame_matrix(in->format);  // (smr_validate_frame has checked the tag)
+    // planar and semi-planar Y'CbCr: which instantiation, which planes (the kernels sample the chroma planes at their own size: 4:2:0, 4:2:2 and
+    // 4:4:4 are one kernel; planes keep a 1x1 placeholder when the logical chroma size is 0)
+    void (*yuv8)(SurfView, SurfView, SurfView, SurfView, int, u32) = nullptr;
+    void (*yuv10)(SurfView, SurfView, SurfView, SurfView, u32) = nullptr;
+    bool semi = false;  // luma + interleaved chroma
     switch (fmt) {
     case SMR_FRAME_PLANAR_YUV420:
     case SMR_FRAME_PLANAR_YUV422:
     case SMR_FRAME_PLANAR_YUV444:
-    case SMR_FRAME_PLANAR_YUVJ420: {
-        if (!in->planes[1] || !in->planes[2]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing chroma plane");
-        SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]), vp = view_of(in->planes[2]);
-        // planes keep a 1x1 placeholder when the logical chroma size is 0; sample with the logical size
-        hipLaunchKernelGGL(k_yuv_to_rgba<0>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, vp, dst,
-                           fmt == SMR_FRAME_PLANAR_YUVJ420 ? 1 : 0, matrix);
-        break;
-    }
-    case SMR_FRAME_NV12: {
-        if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
-        SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
-        hipLaunchKernelGGL(k_yuv_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst, 0, matrix);
-        break;
-    }
-    case SMR_FRAME_PLANAR_YUV420P10: {
-        if (!in->planes[1] || !in->planes[2]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing chroma plane");
-        hipLaunchKernelGGL(k_yuv_hi_to_rgba<0>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), view_of(in->planes[1]),
-                           view_of(in->planes[2]), dst, matrix);
-        break;
-    }
-    case SMR_FRAME_P010: {
-        if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
-        SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
-        hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst, matrix);
-        break;
-    }
-    case SMR_FRAME_PLANAR_YUV422P10: {  // (k_yuv_hi_to_rgba samples the planes at their own size: (w / 2) x h here)
-        if (!in->planes[1] || !in->planes[2]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing chroma plane");
-        hipLaunchKernelGGL(k_yuv_hi_to_rgba<0>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), view_of(in->planes[1]),
-                           view_of(in->planes[2]), dst, matrix);
-        break;
-    }
-    case SMR_FRAME_P210: {
-        if (!in->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing UV plane");
-        SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]);
-        hipLaunchKernelGGL(k_yuv_hi_to_rgba<1>, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, up, dst, matrix);
-        break;
-    }
+    case SMR_FRAME_PLANAR_YUVJ420: yuv8 = k_yuv_to_rgba<0>; break;
+    case SMR_FRAME_NV12: yuv8 = k_yuv_to_rgba<1>; semi = true; break;
+    case SMR_FRAME_PLANAR_YUV420P10:
+    case SMR_FRAME_PLANAR_YUV422P10: yuv10 = k_yuv_hi_to_rgba<0>; break;
+    case SMR_FRAME_P010:
+    case SMR_FRAME_P210: yuv10 = k_yuv_hi_to_rgba<1>; semi = true; break;
     case SMR_FRAME_V210:
         hipLaunchKernelGGL(k_yuv422_hi_to_rgba_any<CV422_V210>, grid_px(w, h), dim3(BLOCK), 0, ctx->stream, view_of(in->planes[0]), dst, matrix);
         break;
@@ -875,6 +747,12 @@ static int smr_frame_to_rgba_general(smr_ctx *ctx, const smr_frame *in, smr_surf
         break;
     default:
         return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: unknown frame format %u", in->format);
+    }
+    if (yuv8 || yuv10) {
+        if (!in->planes[1] || (!semi && !in->planes[2])) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_to_rgba: missing %s plane", semi ? "UV" : "chroma");
+        const SurfView yp = view_of(in->planes[0]), up = view_of(in->planes[1]), vp = semi ? up : view_of(in->planes[2]);
+        if (yuv8) hipLaunchKernelGGL(yuv8, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, vp, dst, fmt == SMR_FRAME_PLANAR_YUVJ420 ? 1 : 0, matrix);
+        else hipLaunchKernelGGL(yuv10, grid_px((w + 3) / 4, h), dim3(BLOCK), 0, ctx->stream, yp, up, vp, dst, matrix);
     }
     SMR_HIP(ctx, hipGetLastError());
     return SMR_OK;

@@ -25,132 +25,7 @@
 // profiles/r04_planar_nodes.txt).
 #pragma once
 
-#include "smr_convert_dev.h"
-
-#ifdef SMR_EMU
-#define cv_perm(hi, lo, sel) dev_perm((hi), (lo), (sel))
-#define cv_alignbyte(hi, lo, sh) dev_alignbyte((hi), (lo), (sh))
-#define cv_clamp01(x) dev_fmed3((x), 0.0f, 1.0f)
-#define cv_mad24(a, b, c) dev_mad24((a), (b), (c))
-#define cv_uniform(x) (x)
-#else
-#define cv_uniform(x) __builtin_amdgcn_readfirstlane(x)  // a value every lane of the wave holds alike, moved to a scalar register
-#define cv_perm(hi, lo, sel) __builtin_amdgcn_perm((hi), (lo), (sel))
-#define cv_alignbyte(hi, lo, sh) __builtin_amdgcn_alignbyte((hi), (lo), (sh))
-#define cv_clamp01(x) __builtin_amdgcn_fmed3f((x), 0.0f, 1.0f)
-#define cv_mad24(a, b, c) ((u32)__umul24((a), (b)) + (c))  // row * pitch + offset with both factors below 2^24: one full-rate v_mad_u32_u24 (a 32 x 32 multiply is a quarter-rate v_mad_u64_u32)
-#endif
-
-// ---- the unorm8 store of a row's twelve values: floor(clamp(x, 0, 1) * 255 + 0.5) (planar_yuv_to_rgba.wgsl:57 through the Rgba8Unorm target).
-// v_cvt_pk_u8_f32 converts, saturates to [0, 255] and inserts the byte into a dword in ONE instruction — with the wave's f32 rounding mode:
-// round-to-nearest-even by default (tools/ubench/cvt_pk_u8.hip: not the reference's truncation), but under round-toward-zero exactly the
-// truncation (tools/ubench/cvt_pk_u8_mode.hip on the device: every f32 within 4 ulp of every integer and half-integer of [0, 258), a sweep of
-// [-2, 298] and the specials — 4.2 M values, no difference from trunc(clamp(x, 0, 255))).  The operands t = x * 255 + 0.5 are computed before, in the
-// default mode, WITHOUT the clamp (t <= 0.5 truncates / saturates to 0 like clamp's 0.5, t >= 255.5 saturates to 255 like clamp's 255.5; NaN
-// cannot occur); the mode is switched inside one asm block around the twelve conversions, so no other float instruction can be scheduled into
-// the switched region.  Three instructions per value (multiply, add, convert) instead of five (median, multiply, add, convert, shift-or).
-// dst[c] |= byte i of channel c for the row's pixel i: RGB12 rows are (R x 4, G x 4, B x 4) dwords; RGBA8 rows take cv_store_px.
-#ifdef SMR_EMU
-static inline u32 cv_emu_u8(float t) { return t >= 255.0f ? 255u : (t > 0.0f ? (u32)t : 0u); }
-#define CV_U8X4(d, t0, t1, t2, t3) do { (d) = cv_emu_u8(t0) | (cv_emu_u8(t1) << 8) | (cv_emu_u8(t2) << 16) | (cv_emu_u8(t3) << 24); } while (0)
-static inline void cv_row_bytes_planar(const float (&t)[3][4], u32 &r4, u32 &g4, u32 &b4) {
-    CV_U8X4(r4, t[0][0], t[0][1], t[0][2], t[0][3]); CV_U8X4(g4, t[1][0], t[1][1], t[1][2], t[1][3]); CV_U8X4(b4, t[2][0], t[2][1], t[2][2], t[2][3]);
-}
-static inline void cv_row_bytes_packed(const float (&t)[3][4], u32 (&px)[4]) {
-    for (int i = 0; i < 4; i++) px[i] = cv_emu_u8(t[0][i]) | (cv_emu_u8(t[1][i]) << 8) | (cv_emu_u8(t[2][i]) << 16) | 0xff000000u;
-}
-#else
-__device__ __forceinline__ void cv_row_bytes_planar(const float (&t)[3][4], u32 &r4, u32 &g4, u32 &b4) {
-    u32 r = 0u, g = 0u, b = 0u;
-    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\ts_nop 1\n\t"
-                 "v_cvt_pk_u8_f32 %0, %3, 0, %0\n\tv_cvt_pk_u8_f32 %1, %7, 0, %1\n\tv_cvt_pk_u8_f32 %2, %11, 0, %2\n\t"
-                 "v_cvt_pk_u8_f32 %0, %4, 1, %0\n\tv_cvt_pk_u8_f32 %1, %8, 1, %1\n\tv_cvt_pk_u8_f32 %2, %12, 1, %2\n\t"
-                 "v_cvt_pk_u8_f32 %0, %5, 2, %0\n\tv_cvt_pk_u8_f32 %1, %9, 2, %1\n\tv_cvt_pk_u8_f32 %2, %13, 2, %2\n\t"
-                 "v_cvt_pk_u8_f32 %0, %6, 3, %0\n\tv_cvt_pk_u8_f32 %1, %10, 3, %1\n\tv_cvt_pk_u8_f32 %2, %14, 3, %2\n\t"
-                 "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1"
-                 : "+v"(r), "+v"(g), "+v"(b)
-                 : "v"(t[0][0]), "v"(t[0][1]), "v"(t[0][2]), "v"(t[0][3]), "v"(t[1][0]), "v"(t[1][1]), "v"(t[1][2]), "v"(t[1][3]), "v"(t[2][0]), "v"(t[2][1]),
-                   "v"(t[2][2]), "v"(t[2][3]));
-    r4 = r; g4 = g; b4 = b;
-}
-__device__ __forceinline__ void cv_row_bytes_packed(const float (&t)[3][4], u32 (&px)[4]) {
-    u32 p0 = 0xff000000u, p1 = 0xff000000u, p2 = 0xff000000u, p3 = 0xff000000u;
-    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\ts_nop 1\n\t"
-                 "v_cvt_pk_u8_f32 %0, %4, 0, %0\n\tv_cvt_pk_u8_f32 %1, %5, 0, %1\n\tv_cvt_pk_u8_f32 %2, %6, 0, %2\n\tv_cvt_pk_u8_f32 %3, %7, 0, %3\n\t"
-                 "v_cvt_pk_u8_f32 %0, %8, 1, %0\n\tv_cvt_pk_u8_f32 %1, %9, 1, %1\n\tv_cvt_pk_u8_f32 %2, %10, 1, %2\n\tv_cvt_pk_u8_f32 %3, %11, 1, %3\n\t"
-                 "v_cvt_pk_u8_f32 %0, %12, 2, %0\n\tv_cvt_pk_u8_f32 %1, %13, 2, %1\n\tv_cvt_pk_u8_f32 %2, %14, 2, %2\n\tv_cvt_pk_u8_f32 %3, %15, 2, %3\n\t"
-                 "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0\n\ts_nop 1"
-                 : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3)
-                 : "v"(t[0][0]), "v"(t[0][1]), "v"(t[0][2]), "v"(t[0][3]), "v"(t[1][0]), "v"(t[1][1]), "v"(t[1][2]), "v"(t[1][3]), "v"(t[2][0]), "v"(t[2][1]),
-                   "v"(t[2][2]), "v"(t[2][3]));
-    px[0] = p0; px[1] = p1; px[2] = p2; px[3] = p3;
-}
-#endif
-
-struct ConvJob {
-    SurfView yp, up, vp, dst;
-    int full, nv;  // full range (J420) | NV12 (interleaved chroma in `up`)
-    int sx, sy;    // chroma subsampling: 4:2:0 = (1, 1), 4:2:2 = (1, 0), 4:4:4 = (0, 0)
-    int rgb12;     // k_yuv420_to_rgba only: dst is an R8 surface of 3 w x h — the node texture as 12-byte groups of four pixels (R x 4, G x 4, B x 4)
-    int packed;    // 0 planar / NV12 | 1 UYVY | 2 YUYV: `yp` is the (w / 2) x h plane of U Y0 V Y1 / Y0 U Y1 V groups | 3 BGRA | 4 ARGB: `yp` is the w x h plane, bytes permuted (bgra_to_rgba.wgsl / argb_to_rgba.wgsl:24-28)
-    int matrix;    // smr_color_matrix of the frame (0 = BT.709, what a zeroed job means).  k_yuv420_to_rgba[_tight] do NOT read it: their matrix is a template parameter and the host queues their jobs per matrix
-};
-constexpr int MAX_CONV_JOBS = 16;
-struct ConvBatch {
-    ConvJob j[MAX_CONV_JOBS];
-    // k_yuv420_to_rgba: the launch's work in UNITS — a unit = 64 column groups (256 pixels) x one block row (4 rows) of one job, what a wave
-    // computes per cv420_run step — dealt to the XCDs in BANDS (cv420_plan): a band = `band` consecutive block rows of a job across all its
-    // column blocks, band g of the launch (jobs one after the other) belongs to XCD g % 8.  Inside an XCD the units are ordered band by band,
-    // column block by column block, block rows fastest, and cut into equal contiguous shares, one per wave the XCD runs (workgroup b runs on
-    // XCD b % 8 — observed, used for locality only: the partition is arithmetic on blockIdx and complete whatever the placement).
-    // Why bands: a column block's chroma window reaches a byte or two into its neighbours' cache lines; neighbours on different XCDs made
-    // every L2 fetch three lines for one (counters: 62 MB for 24.9 MB of planes with shares dealt without regard to the XCDs).
-    int n;
-    u32 band;                                  // block rows per band
-    u32 rows[MAX_CONV_JOBS];                   // block rows of job j
-    u32 cols[MAX_CONV_JOBS];                   // column blocks of job j
-    u32 band0[MAX_CONV_JOBS];                  // launch-wide index of job j's first band
-    u32 first_unit[8][MAX_CONV_JOBS + 1];      // per XCD x: job j owns units [first_unit[x][j], first_unit[x][j + 1]) of x's sequence
-};
-
-// Fills the partition tables of a launch of n jobs (j[].dst.w / .h set) that will run `waves` waves in all; returns the number of bands
-// (the launch needs at least min(8, bands) workgroups: every XCD that owns units must run a wave).
-inline u32 cv420_plan(ConvBatch &B, int n, u32 waves) {
-    B.n = n;
-    u32 total = 0;
-    for (int j = 0; j < n; j++) {
-        B.cols[j] = ((u32)B.j[j].dst.w + 255u) / 256u;
-        B.rows[j] = ((u32)B.j[j].dst.h + 3u) / 4u;
-        total += B.cols[j] * B.rows[j];
-    }
-    // Band height: every share of a band runs on the band's XCD whatever its length, so a band may be much taller than a share — and the
-    // taller, the fewer chroma rows two XCDs both fetch (a band's window reaches one chroma row into the bands above and below: 2 rows per
-    // band of 2 * band).  Against that, the XCDs' totals differ by up to one band: sixteen bands per XCD and more keeps that under a
-    // sixteenth (8 x 1080p: bands of 16 block rows, 17 per XCD, 6 % of the chroma rows fetched twice).
-    (void)waves;
-    u32 cols_max = 1;
-    for (int j = 0; j < n; j++) cols_max = B.cols[j] > cols_max ? B.cols[j] : cols_max;
-    const u32 band = total / (128u * cols_max);
-    B.band = band < 1u ? 1u : (band > 64u ? 64u : band);
-    u32 g = 0;
-    for (int x = 0; x < 8; x++) B.first_unit[x][0] = 0;
-    for (int j = 0; j < n; j++) {
-        B.band0[j] = g;
-        const u32 bands = (B.rows[j] + B.band - 1u) / B.band;
-        u32 units[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (u32 b = 0; b < bands; b++) {
-            const u32 h = B.rows[j] - b * B.band < B.band ? B.rows[j] - b * B.band : B.band;
-            units[(g + b) & 7u] += B.cols[j] * h;
-        }
-        for (int x = 0; x < 8; x++) B.first_unit[x][j + 1] = B.first_unit[x][j] + units[x];
-        g += bands;
-    }
-    return g;
-}
-
-#ifndef CV_ABL
-#define CV_ABL 0  // laboratory builds (tools/variant.sh NAME -DCV_ABL=n): 1 no stores | 2 no chroma loads | 4 no luma loads | 8 no per-pixel arithmetic
-#endif
+#include "smr_convert_batch.h"  // the jobs of a launch, their partition and its walk, the pixel tail, the row sinks: shared with the 10-bit converters
 
 #ifdef __HIPCC__
 
@@ -266,30 +141,15 @@ __device__ __forceinline__ void cv420_hrow(const Cv420Raw<NV> &R, const Cv420Win
 // The four luma rows of block (g, P) from its luma dwords and the window's four chroma rows H[window row][plane][column]:
 // row 4 P + r takes window rows (0, 1) with fy = .75, (1, 2) with .25, (1, 2) with .75, (2, 3) with .25 — top * (1 - fy) + bot * fy:
 // the 3/4 product of window row 1 serves luma rows 0 and 1, that of row 2 serves rows 2 and 3.
-// (c - 16/255) / 0.8784 as RN(a * y_hi + RN(a * y_lo)) with y_hi + y_lo = 1 / 0.8784 to 48 bits: the IEEE quotient for EVERY f32 a in
-// [-16/255, 1] — all 636 524 221 of them checked against the division (tools/check_div_by_constant.py), as unorm_of_byte's form is
-// for the 256 bytes.  One multiply and one fused multiply-add.
 // ALLROWS: the caller knows that all four rows of the block exist (every block of a run but its last): no branch around the stores, so the
 // compiler can count the stores in flight and wait for the NEXT block's loads — requested before them — with vmcnt(stores) instead of vmcnt(0)
 // (the memory counter counts loads and stores alike: with the branch every block waited for its own stores' round trip)
 // SINK: where a finished row goes — sink(r, y, r4, g4, b4, px): row r of the block = frame row y, as RGB12 dwords (RGB12) or four RGBA8 pixels.
 // The default stores into the job's node texture; k_ingest_wave's plane-source builds (smr_ingest_wave.h) hand the rows to LDS instead.
-struct Cv420StoreNode {
-    const ConvJob &J;
-    int g;
-    bool rgb12;
-    __device__ __forceinline__ void operator()(int, int y, u32 r4, u32 g4, u32 b4, const u32 (&px)[4]) const {
-        if (rgb12) g_st_u32x3(J.dst.ptr + cv_mad24((u32)y, J.dst.pitch, 12u * (u32)g), r4, g4, b4);
-        else g_st_u32x4(J.dst.ptr + cv_mad24((u32)y, J.dst.pitch, 16u * (u32)g), make_uint4(px[0], px[1], px[2], px[3]));
-    }
-};
 // MATRIX: the frame's smr_color_matrix, a compile-time property of the launch — the instantiations differ in four literals
 template <bool RGB12, bool FULL, bool ALLROWS, typename SINK, int MATRIX = SMR_MATRIX_BT709>
 __device__ __forceinline__ void cv420_rows_to(const ConvJob &J, int g, int P, const u32 yrow[4], const float H[4][2][4], const float *ylut, const SINK &sink) {
     const int h = J.dst.h;
-    constexpr bool full = FULL;  // (a template parameter: as a run-time flag it was a scalar branch per pixel)
-    constexpr float kc = 0.87843137254f;
-    constexpr float rc_hi = 1.0f / kc, rc_lo = (float)(1.0 / (double)kc - (double)rc_hi);
     constexpr SmrMatrixCoef C = smr_matrix_coef((uint32_t)MATRIX);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -297,43 +157,30 @@ __device__ __forceinline__ void cv420_rows_to(const ConvJob &J, int g, int P, co
         if (!ALLROWS && y >= h) break;
         const int j34 = r < 2 ? 1 : 2, j14 = r == 0 ? 0 : (r == 1 ? 2 : (r == 2 ? 1 : 3));
         const u32 y4 = yrow[r];
-        u32 px[4] = {0u, 0u, 0u, 0u}, r4 = 0u, g4 = 0u, b4 = 0u;
-        float t[3][4];  // x * 255 + 0.5 of the row's twelve values (cv_row_bytes_* truncates and packs them)
+        if (CV_ABL & 8) {  // (laboratory: bytes that keep the loads live, none of the per-pixel arithmetic)
+            u32 px[4] = {0u, 0u, 0u, 0u}, r4 = 0u, g4 = 0u, b4 = 0u;
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            if (CV_ABL & 8) {
+            for (int i = 0; i < 4; i++) {
                 const u32 b = (y4 >> (8 * i)) & 0xffu;
                 px[i] = b | (__float_as_uint(H[j14][0][i] + H[j34][1][i]) & 0xffff00u) | 0xff000000u;
                 r4 |= b << (8 * i); g4 |= (__float_as_uint(H[j14][0][i]) & 0xffu) << (8 * i); b4 |= (__float_as_uint(H[j34][1][i]) & 0xffu) << (8 * i);
-                continue;
             }
-            float u = __builtin_fmaf(H[j14][0][i], 0.25f, H[j34][0][i] * 0.75f);
-            float v = __builtin_fmaf(H[j14][1][i], 0.25f, H[j34][1][i] * 0.75f);
-            const float yy = ylut[(y4 >> (8 * i)) & 0xffu];
-            if (!full) {  // planar_yuv_to_rgba.wgsl:47-48: (c - 16/255) / 0.8784, clamp
-                const float au = u - (16.0f / 255.0f), av = v - (16.0f / 255.0f);
-                u = cv_clamp01(__builtin_fmaf(au, rc_hi, au * rc_lo));
-                v = cv_clamp01(__builtin_fmaf(av, rc_hi, av * rc_lo));
-            }
-            const float um = u - 0.5f, vm = v - 0.5f;
-            const float R = yy + C.rv * vm;
-            const float G = yy - C.gu * um - C.gv * vm;
-            const float B = yy + C.bu * um;
-            t[0][i] = R * 255.0f + 0.5f;
-            t[1][i] = G * 255.0f + 0.5f;
-            t[2][i] = B * 255.0f + 0.5f;
+            cv_sink_row(r, y, r4, g4, b4, px, sink);
+            continue;
         }
-        if (!(CV_ABL & 8)) {
-            if (RGB12) cv_row_bytes_planar(t, r4, g4, b4);
-            else cv_row_bytes_packed(t, px);
+        float t[3][4];  // x * 255 + 0.5 of the row's twelve values
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float u = __builtin_fmaf(H[j14][0][i], 0.25f, H[j34][0][i] * 0.75f);
+            const float v = __builtin_fmaf(H[j14][1][i], 0.25f, H[j34][1][i] * 0.75f);
+            cv_pixel<FULL>(ylut[(y4 >> (8 * i)) & 0xffu], u, v, C, t, i);  // (FULL a template parameter: as a run-time flag it was a scalar branch per pixel)
         }
-        if ((CV_ABL & 1) && (r4 ^ g4 ^ b4 ^ px[0] ^ px[3]) != 0x12345677u) continue;  // (never equal in practice: the values stay live)
-        sink(r, y, r4, g4, b4, px);
+        cv_pack_row<RGB12>(t, r, y, sink);
     }
 }
 template <bool RGB12, bool FULL, bool ALLROWS = false, int MATRIX = SMR_MATRIX_BT709>
 __device__ __forceinline__ void cv420_rows(const ConvJob &J, int g, int P, const u32 yrow[4], const float H[4][2][4], const float *ylut) {
-    cv420_rows_to<RGB12, FULL, ALLROWS, Cv420StoreNode, MATRIX>(J, g, P, yrow, H, ylut, Cv420StoreNode{J, g, RGB12});
+    cv420_rows_to<RGB12, FULL, ALLROWS, CvStoreNode, MATRIX>(J, g, P, yrow, H, ylut, CvStoreNode{J, g, RGB12});
 }
 
 // One 4 x 4 block: columns 4 g .. 4 g + 3, rows 4 P .. 4 P + 3 of job J (rows past the frame's height are not stored).
@@ -407,74 +254,23 @@ __device__ __forceinline__ void cv420_run(const ConvJob &J, int g, int P0, int n
     if (P == P0) CV_STAMP(st, 4, "s_nop 0");
 }
 
-// A job's geometry as VALUES in scalar registers.  Read in place (B.j[j].dst.pitch ...) the compiler treats the kernel-argument segment as
-// memory it may re-read whenever that is cheaper than keeping a register: it did, behind every row's store — an s_load_dword plus
-// s_waitcnt lgkmcnt(0) (scalar loads return out of order, so the wait also drains the table gathers in flight) per row, ~200 cycles
-// each, in every wave at once.  A value that went through v_readfirstlane is a computed value: it stays where it is.
-__device__ __forceinline__ SurfView cv420_view_in_registers(const SurfView &v) {
-#ifdef SMR_EMU
-    return v;
-#else
-    SurfView r;
-    const unsigned long long p = (unsigned long long)(uintptr_t)v.ptr;
-    const u32 lo = cv_uniform((u32)p), hi = cv_uniform((u32)(p >> 32));
-    r.ptr = (u8 *)(uintptr_t)(((unsigned long long)hi << 32) | lo);
-    r.pitch = cv_uniform(v.pitch);
-    r.w = cv_uniform(v.w);
-    r.h = cv_uniform(v.h);
-    return r;
-#endif
-}
-__device__ __forceinline__ ConvJob cv420_job_in_registers(const ConvJob &j) {
-    ConvJob J = j;
-    J.yp = cv420_view_in_registers(j.yp); J.up = cv420_view_in_registers(j.up); J.vp = cv420_view_in_registers(j.vp); J.dst = cv420_view_in_registers(j.dst);
-    J.matrix = (int)cv_uniform((u32)j.matrix);  // (read by the 10-bit converters only)
-    return J;
-}
-
-// Wave `wave` (0 .. 3) of workgroup `block` of a launch of `grid` workgroups: XCD x = block % 8 runs the workgroups x, x + 8, ...; its
-// waves cut x's unit sequence (ConvBatch) into equal contiguous shares — total / waves units, the first total % waves waves one more.  A
-// share is a vertical run of blocks inside one (band, column block) cell, or the end of a cell and the start of the next (in the next
-// band or job, too).  ylut: the limited-range luma table; nlut: byte / 255, which is also the full-range luma table.
-// MATRIX: every job of the launch has this matrix (the host queues k_yuv420_to_rgba's jobs per matrix: smr_frames_to_rgba_batch)
+// A wave's share of a launch (cv_share_walk) over cv420_run.  ylut: the limited-range luma table; nlut: byte / 255, which is also the
+// full-range luma table.  MATRIX: every job of the launch has this matrix (the host queues k_yuv420_to_rgba's jobs per matrix).
+// st: timing builds — only the share's first run is stamped phase by phase (the stamping lane 0's column group exists in every run).
 template <bool NV, bool TIGHT = false, int MATRIX = SMR_MATRIX_BT709>
 __device__ __forceinline__ void cv420_share(const ConvBatch &B, u32 block, u32 wave, u32 grid, u32 lane, const float *ylut, const float *nlut,
                                             unsigned long long *st = nullptr) {
-    const u32 x = block & 7u;
-    const u32 waves = ((grid - x + 7u) >> 3) * 4u, w = (block >> 3) * 4u + wave;  // of this XCD
-    const u32 total = B.first_unit[x][B.n];
-    const u32 share = total / waves, extra = total - share * waves;
-    u32 lo = w * share + (w < extra ? w : extra);
-    const u32 hi = lo + share + (w < extra ? 1u : 0u);
-    int j = 0;
-    while (lo < hi) {  // (uniform: one or two runs per share, more only across tiny jobs)
-#pragma unroll 1
-        while (lo >= B.first_unit[x][j + 1]) j++;
-        const ConvJob J = cv420_job_in_registers(B.j[j]);
-        const u32 rows = B.rows[j], cols = B.cols[j], band = B.band;
-        // x's bands of job j: b0, b0 + 8, ...; all but the job's last band (which, if x owns it, is the last of them) hold cols * band units
-        const u32 b0 = (x - B.band0[j]) & 7u;
-        const u32 local = lo - B.first_unit[x][j];
-        const u32 t = local / (cols * band), b = b0 + 8u * t;
-        const u32 in_band = local - t * cols * band;
-        const u32 band_rows = rows - b * band < band ? rows - b * band : band;
-        const u32 col = in_band / band_rows, r = in_band - col * band_rows;
-        const u32 nrun = hi - lo < band_rows - r ? hi - lo : band_rows - r;
-        const int g = (int)(col * 64u + lane);
-        if (4 * g < J.dst.w) {
-            const int P0 = (int)(b * band + r);
-            // (uniform branches: a job is one frame; range and node format are template parameters — as run-time flags they cost a scalar branch per pixel)
-            if (J.rgb12) {
-                if (J.full) cv420_run<NV, true, true, TIGHT, MATRIX>(J, g, P0, (int)nrun, nlut, nlut, st);
-                else cv420_run<NV, true, false, TIGHT, MATRIX>(J, g, P0, (int)nrun, ylut, nlut, st);
-            } else {
-                if (J.full) cv420_run<NV, false, true, TIGHT, MATRIX>(J, g, P0, (int)nrun, nlut, nlut, st);
-                else cv420_run<NV, false, false, TIGHT, MATRIX>(J, g, P0, (int)nrun, ylut, nlut, st);
-            }
+    cv_share_walk(B, block, wave, grid, lane, [&](const ConvJob &J, int g, int P0, int nrun) {
+        // (uniform branches: a job is one frame; range and node format are template parameters — as run-time flags they cost a scalar branch per pixel)
+        if (J.rgb12) {
+            if (J.full) cv420_run<NV, true, true, TIGHT, MATRIX>(J, g, P0, nrun, nlut, nlut, st);
+            else cv420_run<NV, true, false, TIGHT, MATRIX>(J, g, P0, nrun, ylut, nlut, st);
+        } else {
+            if (J.full) cv420_run<NV, false, true, TIGHT, MATRIX>(J, g, P0, nrun, nlut, nlut, st);
+            else cv420_run<NV, false, false, TIGHT, MATRIX>(J, g, P0, nrun, ylut, nlut, st);
         }
-        st = nullptr;  // (timing builds: only the share's first run is stamped phase by phase)
-        lo += nrun;
-    }
+        st = nullptr;
+    });
 }
 
 #endif  // __HIPCC__

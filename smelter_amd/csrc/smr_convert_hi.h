@@ -9,12 +9,12 @@
 // byte for byte, the node texture of the 8-bit frame with bytes b; the node texture itself is the 8-bit converter's RGBA8 / RGB12, so the
 // resampler, the compositor, the node cache and the gather see nothing new.
 //
-// The block converter has k_yuv420_to_rgba's shape (smr_convert_420.h): a thread owns a 4 x 4 pixel block, cv420_plan's XCD bands and equal
+// The block converter has k_yuv420_to_rgba's shape (smr_convert_420.h): a thread owns a 4 x 4 pixel block, cv_plan's XCD bands and equal
 // shares, vertical runs that keep the two chroma window rows neighbouring blocks share, all of a block's loads in flight before its first
 // store, one 16-byte (RGB12: 12-byte) store per thread and row.  What differs is the fetch — a luma row of a block is 8 bytes, a P010 chroma
 // window four U V dwords, a planar window 8 bytes starting on an odd word — and the tables: two of 1024 entries (8 KB of LDS per workgroup).
-// The arithmetic from the lerps to cv_row_bytes_* is cv420_hrow's and cv420_rows_to's, statement for statement; it is DUPLICATED here, not
-// shared, so that the 8-bit kernels stay the instruction streams they were measured as (the share walk likewise).
+// The lerps are cv420_hrow's and cv420_rows_to's, statement for statement; the share walk, the pixel tail and the row's way out are the
+// shared ones (smr_convert_batch.h).
 //
 // ONE MEMORY CONTRACT, for planes the library owns and planes it wraps alike: no byte outside [0, row bytes) of any plane row is requested.
 // Where a window's last column is the plane's edge the load of the column behind it is aimed at the edge column again.
@@ -129,7 +129,7 @@ __device__ __forceinline__ CvHiRaw<P010> cvhi_load_chroma(const ConvJob &J, cons
     }
     return R;
 }
-// a luma row of a block: four words, 8 bytes (rows and the plane are 8-byte aligned: conv_hi_mode)
+// a luma row of a block: four words, 8 bytes (rows and the plane are 8-byte aligned: conv_route)
 __device__ __forceinline__ void cvhi_load_luma(const ConvJob &J, int g, int P, uint2 yrow[4]) {
     const int h = J.dst.h;
 #pragma unroll
@@ -166,47 +166,34 @@ __device__ __forceinline__ void cvhi_hrow(const CvHiRaw<P010> &R, const CvHiWin 
     }
 }
 
+// the four luma codes of a row of a block
+template <bool P010>
+__device__ __forceinline__ void cvhi_row_codes(uint2 y4, u32 (&c)[4]) {
+    c[0] = cvhi_code_lo<P010>(y4.x); c[1] = cvhi_code_hi<P010>(y4.x); c[2] = cvhi_code_lo<P010>(y4.y); c[3] = cvhi_code_hi<P010>(y4.y);
+}
+
 // The four luma rows of block (g, P) from its luma words and the window's four chroma rows H[window row][plane][column]: cv420_rows_to's
-// statements (limited range) with the luma table indexed by the 10-bit code.
-// The chroma range division keeps rc_hi / rc_lo: their exhaustive proof (tools/check_div_by_constant.py) covers every f32 in [-16/255, 1],
-// and the 10-bit operand u - 16/255 has u <= 255.75 / 255 (a lerp of unorm values of codes <= 1023, weights summing to 1, each rounding
-// monotone), so it stays inside that interval.
+// vertical lerps, then the shared pixel tail (limited range) with the luma table indexed by the 10-bit code.
 template <bool P010, bool RGB12, bool ALLROWS>
 __device__ __forceinline__ void cvhi_rows(const ConvJob &J, int g, int P, const uint2 yrow[4], const float H[4][2][4], const float *ylut) {
     const int h = J.dst.h;
-    constexpr float kc = 0.87843137254f;
-    constexpr float rc_hi = 1.0f / kc, rc_lo = (float)(1.0 / (double)kc - (double)rc_hi);
-    const SmrMatrixCoef C = smr_matrix_coef((u32)J.matrix);  // (uniform: the job's matrix sits in a scalar register, cv420_job_in_registers; not on the benchmark's path, so no instantiation per matrix)
-    const Cv420StoreNode sink{J, g, RGB12};
+    const SmrMatrixCoef C = smr_matrix_coef((u32)J.matrix);  // (uniform: the job's matrix sits in a scalar register, cv_job_in_registers; not on the benchmark's path, so no instantiation per matrix)
+    const CvStoreNode sink{J, g, RGB12};
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int y = 4 * P + r;
         if (!ALLROWS && y >= h) break;
         const int j34 = r < 2 ? 1 : 2, j14 = r == 0 ? 0 : (r == 1 ? 2 : (r == 2 ? 1 : 3));
-        const uint2 y4 = yrow[r];
-        const u32 yc[4] = {cvhi_code_lo<P010>(y4.x), cvhi_code_hi<P010>(y4.x), cvhi_code_lo<P010>(y4.y), cvhi_code_hi<P010>(y4.y)};
-        u32 px[4] = {0u, 0u, 0u, 0u}, r4 = 0u, g4 = 0u, b4 = 0u;
-        float t[3][4];  // x * 255 + 0.5 of the row's twelve values (cv_row_bytes_* truncates and packs them)
+        u32 yc[4];
+        cvhi_row_codes<P010>(yrow[r], yc);
+        float t[3][4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            float u = __builtin_fmaf(H[j14][0][i], 0.25f, H[j34][0][i] * 0.75f);
-            float v = __builtin_fmaf(H[j14][1][i], 0.25f, H[j34][1][i] * 0.75f);
-            const float yy = ylut[yc[i]];
-            // planar_yuv_to_rgba.wgsl:47-48: (c - 16/255) / 0.8784, clamp
-            const float au = u - (16.0f / 255.0f), av = v - (16.0f / 255.0f);
-            u = cv_clamp01(__builtin_fmaf(au, rc_hi, au * rc_lo));
-            v = cv_clamp01(__builtin_fmaf(av, rc_hi, av * rc_lo));
-            const float um = u - 0.5f, vm = v - 0.5f;
-            const float R = yy + C.rv * vm;
-            const float G = yy - C.gu * um - C.gv * vm;
-            const float B = yy + C.bu * um;
-            t[0][i] = R * 255.0f + 0.5f;
-            t[1][i] = G * 255.0f + 0.5f;
-            t[2][i] = B * 255.0f + 0.5f;
+            const float u = __builtin_fmaf(H[j14][0][i], 0.25f, H[j34][0][i] * 0.75f);
+            const float v = __builtin_fmaf(H[j14][1][i], 0.25f, H[j34][1][i] * 0.75f);
+            cv_pixel<false>(ylut[yc[i]], u, v, C, t, i);
         }
-        if (RGB12) cv_row_bytes_planar(t, r4, g4, b4);
-        else cv_row_bytes_packed(t, px);
-        sink(r, y, r4, g4, b4, px);
+        cv_pack_row<RGB12>(t, r, y, sink);
     }
 }
 
@@ -245,36 +232,13 @@ __device__ __forceinline__ void cvhi_run(const ConvJob &J, int g, int P0, int nb
     cvhi_rows<P010, RGB12, false>(J, g, P, yrow, H, ylut);
 }
 
-// cv420_share's walk (ConvBatch, cv420_plan: XCD bands, equal contiguous shares per wave) over cvhi_run
+// a wave's share of a launch (cv_share_walk) over cvhi_run
 template <bool P010>
 __device__ __forceinline__ void cvhi_share(const ConvBatch &B, u32 block, u32 wave, u32 grid, u32 lane, const float *ylut, const float *ulut) {
-    const u32 x = block & 7u;
-    const u32 waves = ((grid - x + 7u) >> 3) * 4u, w = (block >> 3) * 4u + wave;  // of this XCD
-    const u32 total = B.first_unit[x][B.n];
-    const u32 share = total / waves, extra = total - share * waves;
-    u32 lo = w * share + (w < extra ? w : extra);
-    const u32 hi = lo + share + (w < extra ? 1u : 0u);
-    int j = 0;
-    while (lo < hi) {  // (uniform: one or two runs per share, more only across tiny jobs)
-#pragma unroll 1
-        while (lo >= B.first_unit[x][j + 1]) j++;
-        const ConvJob J = cv420_job_in_registers(B.j[j]);
-        const u32 rows = B.rows[j], cols = B.cols[j], band = B.band;
-        const u32 b0 = (x - B.band0[j]) & 7u;
-        const u32 local = lo - B.first_unit[x][j];
-        const u32 t = local / (cols * band), b = b0 + 8u * t;
-        const u32 in_band = local - t * cols * band;
-        const u32 band_rows = rows - b * band < band ? rows - b * band : band;
-        const u32 col = in_band / band_rows, r = in_band - col * band_rows;
-        const u32 nrun = hi - lo < band_rows - r ? hi - lo : band_rows - r;
-        const int g = (int)(col * 64u + lane);
-        if (4 * g < J.dst.w) {
-            const int P0 = (int)(b * band + r);
-            if (J.rgb12) cvhi_run<P010, true>(J, g, P0, (int)nrun, ylut, ulut);
-            else cvhi_run<P010, false>(J, g, P0, (int)nrun, ylut, ulut);
-        }
-        lo += nrun;
-    }
+    cv_share_walk(B, block, wave, grid, lane, [&](const ConvJob &J, int g, int P0, int nrun) {
+        if (J.rgb12) cvhi_run<P010, true>(J, g, P0, nrun, ylut, ulut);
+        else cvhi_run<P010, false>(J, g, P0, nrun, ylut, ulut);
+    });
 }
 
 #endif  // __HIPCC__

@@ -11,18 +11,17 @@
 //   * v210 is interleaved_uyvy_to_rgba.wgsl: pixel x takes Y[x] and the chroma of pair x / 2, no interpolation, then yuv_to_rgb_store
 //     (limited range) — for even widths from 8 a frame whose codes are 4 b has the node texture of the UYVY frame with bytes b.
 //
-// The block converter has k_yuv420_hi_to_rgba's shape: a thread owns a 4 x 4 pixel block, cv420_plan's XCD bands and equal shares, block
+// The block converter has k_yuv420_hi_to_rgba's shape: a thread owns a 4 x 4 pixel block, cv_plan's XCD bands and equal shares, block
 // P + 1's loads requested before block P is computed, all of a block's loads in flight before its first store, one 16-byte (RGB12: 12-byte)
-// store per thread and row through Cv420StoreNode, the two 1024-entry tables of cvhi_build_tables.  What differs from 4:2:0 is the fetch:
+// store per thread and row through CvStoreNode, the two 1024-entry tables of cvhi_build_tables.  What differs from 4:2:0 is the fetch:
 //   * planar / P210: each of the block's four luma rows has its OWN chroma row — no vertical lerp, nothing carried between blocks.  The
 //     window and its horizontal lerps are cvhi_window's and cvhi_hrow's (they never ask for the row count); the load is cvhi_load_chroma's
 //     with h rows instead of h / 2;
 //   * v210: thread g's pixels 4 g .. 4 g + 3 live in the 16 bytes at byte 32 (g / 3) + 8 (g % 3) of the row — a 12-pixel, 32-byte period
 //     against the 4-pixel column groups — which always lie inside the row's 16 ceil(w / 6) bytes.  Which of the twelve 10-bit fields are
 //     Y0 .. Y3 and the two chroma pairs depends on g % 3 only: selects, no divergent paths.
-// The arithmetic from the chroma values to cv_row_bytes_* is cvhi_rows's without its two vertical FMAs, statement for statement, DUPLICATED
-// here (and the share walk with it) for the reason smr_convert_hi.h gives: the kernels that exist keep the instruction streams they were
-// measured as.  v210 runs the chroma range division and the matrix products once per pixel pair.
+// From the chroma values on it is the shared pixel tail and share walk (smr_convert_batch.h), without cvhi_rows's two vertical FMAs.  v210 runs
+// the chroma range division and the matrix products once per pixel pair.
 //
 // ONE MEMORY CONTRACT, for planes the library owns and planes it wraps alike: no byte outside [0, row bytes) of any plane row is requested.
 #pragma once
@@ -65,45 +64,24 @@ __device__ __forceinline__ void cv422_load(const ConvJob &J, const CvHiWin &W, i
     for (int r = 0; r < 4; r++) K.c[r] = cv422_load_chroma<P210>(J, W, 4 * P + r);
 }
 
-// The four rows of block (g, P): cvhi_rows's statements (limited range) with the row's own horizontal lerps as u and v.
-// The chroma range division keeps rc_hi / rc_lo: the operand u - 16/255 stays inside the interval of their exhaustive proof for the reason
-// cvhi_rows gives.
+// The four rows of block (g, P): the row's own horizontal lerps as u and v into the shared pixel tail (limited range).
 template <bool P210, bool RGB12, bool ALLROWS>
 __device__ __forceinline__ void cv422_rows(const ConvJob &J, int g, int P, const Cv422Blk<P210> &K, const CvHiWin &W, const float *ylut, const float *ulut) {
     const int h = J.dst.h;
-    constexpr float kc = 0.87843137254f;
-    constexpr float rc_hi = 1.0f / kc, rc_lo = (float)(1.0 / (double)kc - (double)rc_hi);
     const SmrMatrixCoef C = smr_matrix_coef((u32)J.matrix);  // (uniform, as in cvhi_rows)
-    const Cv420StoreNode sink{J, g, RGB12};
+    const CvStoreNode sink{J, g, RGB12};
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int y = 4 * P + r;
         if (!ALLROWS && y >= h) break;
         float H[2][4];
         cvhi_hrow<P210>(K.c[r], W, ulut, H);
-        const uint2 y4 = K.y[r];
-        const u32 yc[4] = {cvhi_code_lo<P210>(y4.x), cvhi_code_hi<P210>(y4.x), cvhi_code_lo<P210>(y4.y), cvhi_code_hi<P210>(y4.y)};
-        u32 px[4] = {0u, 0u, 0u, 0u}, r4 = 0u, g4 = 0u, b4 = 0u;
-        float t[3][4];  // x * 255 + 0.5 of the row's twelve values (cv_row_bytes_* truncates and packs them)
+        u32 yc[4];
+        cvhi_row_codes<P210>(K.y[r], yc);
+        float t[3][4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            float u = H[0][i], v = H[1][i];
-            const float yy = ylut[yc[i]];
-            // planar_yuv_to_rgba.wgsl:47-48: (c - 16/255) / 0.8784, clamp
-            const float au = u - (16.0f / 255.0f), av = v - (16.0f / 255.0f);
-            u = cv_clamp01(__builtin_fmaf(au, rc_hi, au * rc_lo));
-            v = cv_clamp01(__builtin_fmaf(av, rc_hi, av * rc_lo));
-            const float um = u - 0.5f, vm = v - 0.5f;
-            const float R = yy + C.rv * vm;
-            const float G = yy - C.gu * um - C.gv * vm;
-            const float B = yy + C.bu * um;
-            t[0][i] = R * 255.0f + 0.5f;
-            t[1][i] = G * 255.0f + 0.5f;
-            t[2][i] = B * 255.0f + 0.5f;
-        }
-        if (RGB12) cv_row_bytes_planar(t, r4, g4, b4);
-        else cv_row_bytes_packed(t, px);
-        sink(r, y, r4, g4, b4, px);
+        for (int i = 0; i < 4; i++) cv_pixel<false>(ylut[yc[i]], H[0][i], H[1][i], C, t, i);
+        cv_pack_row<RGB12>(t, r, y, sink);
     }
 }
 
@@ -128,7 +106,7 @@ __device__ __forceinline__ void cv422_run(const ConvJob &J, int g, int P0, int n
 
 // ---- v210: the pieces of a block
 
-// the 16 bytes of a row that hold column group g's pixels, as two 8-byte loads (the plane and its pitch are 8-byte aligned: conv_hi422_mode)
+// the 16 bytes of a row that hold column group g's pixels, as two 8-byte loads (the plane and its pitch are 8-byte aligned: conv_route)
 struct Cv210Blk {
     uint2 d[4][2];
 };
@@ -158,10 +136,8 @@ __device__ __forceinline__ u32 cv210_field(const u32 (&e)[4], u32 m, int da, u32
 template <bool RGB12, bool ALLROWS>
 __device__ __forceinline__ void cv210_rows(const ConvJob &J, int g, u32 m, int P, const Cv210Blk &K, const float *ylut, const float *ulut) {
     const int h = J.dst.h;
-    constexpr float kc = 0.87843137254f;
-    constexpr float rc_hi = 1.0f / kc, rc_lo = (float)(1.0 / (double)kc - (double)rc_hi);
     const SmrMatrixCoef C = smr_matrix_coef((u32)J.matrix);  // (uniform, as in cvhi_rows)
-    const Cv420StoreNode sink{J, g, RGB12};
+    const CvStoreNode sink{J, g, RGB12};
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int y = 4 * P + r;
@@ -171,31 +147,22 @@ __device__ __forceinline__ void cv210_rows(const ConvJob &J, int g, u32 m, int P
                            cv210_field(e, m, 1, 20u, 2, 10u, 3, 0u), cv210_field(e, m, 2, 10u, 3, 0u, 3, 20u)};
         const u32 cb[2] = {cv210_field(e, m, 0, 0u, 0, 20u, 1, 10u), cv210_field(e, m, 1, 10u, 2, 0u, 2, 20u)};
         const u32 cr[2] = {cv210_field(e, m, 0, 20u, 1, 10u, 2, 0u), cv210_field(e, m, 2, 0u, 2, 20u, 3, 10u)};
-        u32 px[4] = {0u, 0u, 0u, 0u}, r4 = 0u, g4 = 0u, b4 = 0u;
-        float t[3][4];  // x * 255 + 0.5 of the row's twelve values (cv_row_bytes_* truncates and packs them)
+        float t[3][4];
 #pragma unroll
         for (int p = 0; p < 2; p++) {
-            // interleaved_uyvy_to_rgba.wgsl: the pair's own chroma texel; then (c - 16/255) / 0.8784, clamp.  The operand is at most
-            // 255.75 / 255 - 16/255: inside the interval rc_hi / rc_lo are proven for (tools/check_div_by_constant.py)
-            const float au = ulut[cb[p]] - (16.0f / 255.0f), av = ulut[cr[p]] - (16.0f / 255.0f);
-            const float u = cv_clamp01(__builtin_fmaf(au, rc_hi, au * rc_lo));
-            const float v = cv_clamp01(__builtin_fmaf(av, rc_hi, av * rc_lo));
+            // interleaved_uyvy_to_rgba.wgsl: the pair's own chroma texel (a code's unorm value: inside cv_chroma_expand's proven interval);
+            // cv_pixel's statements with the range expansion and the matrix products once per pair
+            float u = ulut[cb[p]], v = ulut[cr[p]];
+            cv_chroma_expand(u, v);
             const float um = u - 0.5f, vm = v - 0.5f;
-            const float rv = C.rv * vm, gu = C.gu * um, gv = C.gv * vm, bu = C.bu * um;  // (the matrix products: per pair)
+            const float rv = C.rv * vm, gu = C.gu * um, gv = C.gv * vm, bu = C.bu * um;
 #pragma unroll
             for (int i = 2 * p; i < 2 * p + 2; i++) {
                 const float yy = ylut[yc[i]];
-                const float R = yy + rv;
-                const float G = yy - gu - gv;
-                const float B = yy + bu;
-                t[0][i] = R * 255.0f + 0.5f;
-                t[1][i] = G * 255.0f + 0.5f;
-                t[2][i] = B * 255.0f + 0.5f;
+                cv_scale_px(yy + rv, yy - gu - gv, yy + bu, t, i);
             }
         }
-        if (RGB12) cv_row_bytes_planar(t, r4, g4, b4);
-        else cv_row_bytes_packed(t, px);
-        sink(r, y, r4, g4, b4, px);
+        cv_pack_row<RGB12>(t, r, y, sink);
     }
 }
 template <bool RGB12>
@@ -215,41 +182,18 @@ __device__ __forceinline__ void cv210_run(const ConvJob &J, int g, int P0, int n
     cv210_rows<RGB12, false>(J, g, m, P, cur, ylut, ulut);
 }
 
-// cvhi_share's walk (ConvBatch, cv420_plan: XCD bands, equal contiguous shares per wave) over cv422_run / cv210_run
+// a wave's share of a launch (cv_share_walk) over cv422_run / cv210_run
 template <int LAYOUT>
 __device__ __forceinline__ void cv422_share(const ConvBatch &B, u32 block, u32 wave, u32 grid, u32 lane, const float *ylut, const float *ulut) {
-    const u32 x = block & 7u;
-    const u32 waves = ((grid - x + 7u) >> 3) * 4u, w = (block >> 3) * 4u + wave;  // of this XCD
-    const u32 total = B.first_unit[x][B.n];
-    const u32 share = total / waves, extra = total - share * waves;
-    u32 lo = w * share + (w < extra ? w : extra);
-    const u32 hi = lo + share + (w < extra ? 1u : 0u);
-    int j = 0;
-    while (lo < hi) {  // (uniform: one or two runs per share, more only across tiny jobs)
-#pragma unroll 1
-        while (lo >= B.first_unit[x][j + 1]) j++;
-        const ConvJob J = cv420_job_in_registers(B.j[j]);
-        const u32 rows = B.rows[j], cols = B.cols[j], band = B.band;
-        const u32 b0 = (x - B.band0[j]) & 7u;
-        const u32 local = lo - B.first_unit[x][j];
-        const u32 t = local / (cols * band), b = b0 + 8u * t;
-        const u32 in_band = local - t * cols * band;
-        const u32 band_rows = rows - b * band < band ? rows - b * band : band;
-        const u32 col = in_band / band_rows, r = in_band - col * band_rows;
-        const u32 nrun = hi - lo < band_rows - r ? hi - lo : band_rows - r;
-        const int g = (int)(col * 64u + lane);
-        if (4 * g < J.dst.w) {
-            const int P0 = (int)(b * band + r);
-            if (LAYOUT == CV422_V210) {
-                if (J.rgb12) cv210_run<true>(J, g, P0, (int)nrun, ylut, ulut);
-                else cv210_run<false>(J, g, P0, (int)nrun, ylut, ulut);
-            } else {
-                if (J.rgb12) cv422_run<LAYOUT == CV422_P210, true>(J, g, P0, (int)nrun, ylut, ulut);
-                else cv422_run<LAYOUT == CV422_P210, false>(J, g, P0, (int)nrun, ylut, ulut);
-            }
+    cv_share_walk(B, block, wave, grid, lane, [&](const ConvJob &J, int g, int P0, int nrun) {
+        if (LAYOUT == CV422_V210) {
+            if (J.rgb12) cv210_run<true>(J, g, P0, nrun, ylut, ulut);
+            else cv210_run<false>(J, g, P0, nrun, ylut, ulut);
+        } else {
+            if (J.rgb12) cv422_run<LAYOUT == CV422_P210, true>(J, g, P0, nrun, ylut, ulut);
+            else cv422_run<LAYOUT == CV422_P210, false>(J, g, P0, nrun, ylut, ulut);
         }
-        lo += nrun;
-    }
+    });
 }
 
 // ---- v210, any geometry: one pixel.  interleaved_uyvy_to_rgba.wgsl's rule as include/smr.h defines it for every width: luma Y[x], the

@@ -50,7 +50,7 @@ enum {
 };
 
 // Every allocation of the library ends with this many spare bytes: the 4:2:0 block converter reads (and ignores) up to a dword past the last
-// chroma row's end when a row's bytes fill its pitch exactly (smr_convert.hip, conv_420_ok).
+// chroma row's end when a row's bytes fill its pitch exactly (smr_convert.hip, conv_route).
 constexpr size_t SMR_SURFACE_TAIL = 16;
 
 struct smr_surface {
@@ -203,6 +203,7 @@ struct smr_ctx {
     bool rgb12_cls82 = false;    // SMR_RGB12_CLS82=1 (A/B): RGB12 node textures for that class too
     int convert_wg_per_cu = 0;   // SMR_CONVERT_WG_PER_CU (laboratory builds): resident workgroups per CU of the persistent converter launch; 0 = by batch size (smr_convert.hip)
     u32 convert_lds_pad = 0;     // SMR_CONVERT_LDS_PAD (laboratory builds): extra dynamic LDS per workgroup of the block converter, i.e. a cap on its resident workgroups per CU
+    int convert_resident[24] = {};  // resident workgroups per CU of a block converter whose grid is sized by asking (smr_convert.hip), per ConvRoute; 0 = not asked yet
     u32 convert_impl = 0;        // smr_convert_impl (SMR_OPT_CONVERT_IMPL; SMR_CONVERT_GENERAL in the environment sets 1 at creation)
     bool mfma_attr_set = false;  // hipFuncSetAttribute is per device: kept per ctx, not per process
     bool wave_attr_set = false;

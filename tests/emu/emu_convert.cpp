@@ -31,7 +31,7 @@ struct Plane {
     SurfView view;
 };
 // rows on a 256-byte pitch like smr_surface_create's, padding filled with a byte no plane contains by accident; with emu_set_guard(.., 1)
-// on the smallest pitch conv_420_ok (smr_convert.hip) lets through: `min_row` bytes (what the last block's window loads reach), dword-aligned
+// on the smallest pitch conv_route (smr_convert.hip) lets through: `min_row` bytes (what the last block's window loads reach), dword-aligned
 Plane make_plane(const u8 *tight, int w, int h, int bpp, u8 fill, u32 min_row = 0) {
     Plane p;
     u32 pitch = (u32)(((size_t)w * bpp + 255) & ~(size_t)255);
@@ -39,14 +39,14 @@ Plane make_plane(const u8 *tight, int w, int h, int bpp, u8 fill, u32 min_row = 
         pitch = (u32)(((size_t)w * bpp + 3) & ~(size_t)3);
         if (pitch < min_row && !emu_tight) pitch = (min_row + 3u) & ~3u;
     }
-    // (a plane the library allocates ends with SMR_SURFACE_TAIL spare bytes and may be read past a row's end — conv_420_ok's rule for owned
+    // (a plane the library allocates ends with SMR_SURFACE_TAIL spare bytes and may be read past a row's end — conv_route's rule for owned
     //  surfaces; a wrapped one, emu_min_pitch, is exactly pitch * h bytes and is only let through with a pitch that holds the reach)
     p.buf.alloc((size_t)pitch * h + (emu_min_pitch || emu_tight ? 0 : SMR_SURFACE_TAIL), fill, 4);
     for (int y = 0; y < h; y++) memcpy(p.buf.ptr + (size_t)y * pitch, tight + (size_t)y * w * bpp, (size_t)w * bpp);
     p.view.ptr = p.buf.ptr; p.view.pitch = pitch; p.view.w = w; p.view.h = h;
     return p;
 }
-// conv_420_ok's `need`: the last block's chroma window starts at column cw - 3; its bytes begin in the dword at ((cw - 3) [* 2]) & ~3 and
+// conv_route's `need`: the last block's chroma window starts at column cw - 3; its bytes begin in the dword at ((cw - 3) [* 2]) & ~3 and
 // the loads reach 8 (12) bytes from there
 u32 chroma_need(int w, int nv12) {
     const u32 cw = (u32)w / 2;
@@ -115,7 +115,7 @@ extern "C" int emu_convert_420(const u8 *y, const u8 *u, const u8 *v, int w, int
 }
 
 // What a launch of k_yuv420_to_rgba computes: `n` frames of one kind (all planar or all NV12; widths / heights / ranges / node formats per
-// frame) partitioned the way the host does (cv420_plan: bands dealt to the XCDs, equal shares per wave) over `waves` WORKGROUPS, every lane of every wave emulated in turn.
+// frame) partitioned the way the host does (cv_plan: bands dealt to the XCDs, equal shares per wave) over `waves` WORKGROUPS, every lane of every wave emulated in turn.
 // ys / us / vs / outs: n pointers; ws / hs / fulls / rgb12s: n ints.  Output layout per frame as emu_convert_420_run.
 extern "C" int emu_convert_420_shares(int n, const u8 *const *ys, const u8 *const *us, const u8 *const *vs, const int *ws, const int *hs, int nv12,
                                       const int *fulls, const int *rgb12s, int waves, u8 *const *outs) {
@@ -140,9 +140,9 @@ extern "C" int emu_convert_420_shares(int n, const u8 *const *ys, const u8 *cons
         J.dst.ptr = dst[i].ptr; J.dst.pitch = dpitch[i]; J.dst.w = w; J.dst.h = h;
         J.full = fulls[i]; J.nv = nv12; J.sx = 1; J.sy = 1; J.packed = 0; J.rgb12 = rgb12s[i];
     }
-    // `waves` = workgroups here (four waves each), as the host launches them: the partition is the host's own (cv420_plan)
+    // `waves` = workgroups here (four waves each), as the host launches them: the partition is the host's own (cv_plan)
     u32 grid = (u32)waves;
-    const u32 bands = cv420_plan(B, n, grid * 4u);
+    const u32 bands = cv_plan(B, n);
     if (grid < (bands < 8u ? bands : 8u)) grid = bands < 8u ? bands : 8u;  // (as smr_frames_to_rgba_batch does: every XCD that owns a band runs a workgroup)
     float ylut[256], nlut[256];
     for (u32 b = 0; b < 256; b++) {

@@ -25,7 +25,7 @@ struct Plane {
     SurfView view;
 };
 // `w` texels of `bpp` bytes per row.  Rows on a 256-byte pitch like smr_surface_create's, padding filled with a byte no plane contains by
-// accident; with emu_set_guard(.., 1) on the smallest pitch conv_hi_mode (smr_convert.hip) lets through — the row's own bytes (a multiple of 8
+// accident; with emu_set_guard(.., 1) on the smallest pitch conv_route (smr_convert.hip) lets through — the row's own bytes (a multiple of 8
 // for luma, of 4 for chroma at the widths the block converter takes) — and the buffer exactly pitch * h bytes: ONE memory contract.
 Plane make_plane(const u8 *tight, int w, int h, int bpp, u8 fill, size_t align) {
     Plane p;
@@ -96,7 +96,7 @@ extern "C" int emu_convert_hi_run(const u8 *y, const u8 *u, const u8 *v, int w, 
     return F.finish(out, 0xc0de);
 }
 
-// What a launch of k_yuv420_hi_to_rgba computes: `n` frames of one format partitioned the way the host does (cv420_plan) over `waves`
+// What a launch of k_yuv420_hi_to_rgba computes: `n` frames of one format partitioned the way the host does (cv_plan) over `waves`
 // WORKGROUPS, every lane of every wave emulated in turn.  Pointers and ints per frame; output layout per frame as emu_convert_hi_run.
 extern "C" int emu_convert_hi_shares(int n, const u8 *const *ys, const u8 *const *us, const u8 *const *vs, const int *ws, const int *hs, int p010,
                                      const int *rgb12s, int waves, u8 *const *outs) {
@@ -111,7 +111,7 @@ extern "C" int emu_convert_hi_shares(int n, const u8 *const *ys, const u8 *const
         B.j[i] = F[i].job(p010);
     }
     u32 grid = (u32)waves;
-    const u32 bands = cv420_plan(B, n, grid * 4u);
+    const u32 bands = cv_plan(B, n);
     if (grid < (bands < 8u ? bands : 8u)) grid = bands < 8u ? bands : 8u;  // (as smr_frames_to_rgba_batch does: every XCD that owns a band runs a workgroup)
     for (u32 blk = 0; blk < grid; blk++)
         for (u32 wv = 0; wv < 4; wv++)

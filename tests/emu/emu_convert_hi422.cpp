@@ -33,7 +33,7 @@ Plane make_plane(const u8 *tight, int w, int h, int bpp, u32 pitch, u8 fill, siz
     p.view.ptr = p.buf.ptr; p.view.pitch = pitch; p.view.w = w; p.view.h = h;
     return p;
 }
-// emu_set_guard(.., 1): the smallest pitch conv_hi422_mode (smr_convert.hip) lets through — the row's own bytes; otherwise a wide one: the
+// emu_set_guard(.., 1): the smallest pitch conv_route (smr_convert.hip) lets through — the row's own bytes; otherwise a wide one: the
 // allocator's 256-byte pitch, and for v210 a capture card's stride ((w + 47) / 48) * 128: ONE memory contract for both.
 u32 plane_pitch(size_t row_bytes) { return emu_min_pitch ? (u32)row_bytes : (u32)((row_bytes + 255) & ~(size_t)255); }
 u32 v210_pitch(int w) { return emu_min_pitch ? 16u * (u32)((w + 5) / 6) : (u32)((w + 47) / 48) * 128u; }
@@ -116,7 +116,7 @@ extern "C" int emu_convert_hi422_run(const u8 *y, const u8 *u, const u8 *v, int 
     return F.finish(out, 0xc0de);
 }
 
-// What a launch of k_yuv422_hi_to_rgba<layout> computes: `n` frames partitioned the way the host does (cv420_plan) over `waves` WORKGROUPS,
+// What a launch of k_yuv422_hi_to_rgba<layout> computes: `n` frames partitioned the way the host does (cv_plan) over `waves` WORKGROUPS,
 // every lane of every wave emulated in turn.  Pointers and ints per frame; output layout per frame as emu_convert_hi422_run.
 extern "C" int emu_convert_hi422_shares(int n, const u8 *const *ys, const u8 *const *us, const u8 *const *vs, const int *ws, const int *hs, int layout,
                                         const int *rgb12s, int waves, u8 *const *outs) {
@@ -131,7 +131,7 @@ extern "C" int emu_convert_hi422_shares(int n, const u8 *const *ys, const u8 *co
         B.j[i] = F[i].job(layout);
     }
     u32 grid = (u32)waves;
-    const u32 bands = cv420_plan(B, n, grid * 4u);
+    const u32 bands = cv_plan(B, n);
     if (grid < (bands < 8u ? bands : 8u)) grid = bands < 8u ? bands : 8u;  // (as smr_frames_to_rgba_batch does: every XCD that owns a band runs a workgroup)
     for (u32 blk = 0; blk < grid; blk++)
         for (u32 wv = 0; wv < 4; wv++)

@@ -40,7 +40,7 @@ Plane make_plane(const u8 *tight, int w, int h, int bpp, u32 pitch, size_t tail,
     return p;
 }
 // 8-bit chroma planes (emu_convert.cpp's rule): the allocator's 256-byte pitch and tail, or — emu_set_guard(.., 1) — the smallest pitch
-// conv_420_mode lets through: what the last block's window loads reach (plain build), the row's bytes rounded up to a dword (tight build)
+// conv_route lets through: what the last block's window loads reach (plain build), the row's bytes rounded up to a dword (tight build)
 u32 chroma_need(int w, int nv12) {
     const u32 cw = (u32)w / 2;
     return nv12 ? ((2u * (cw - 3u)) & ~3u) + 12u : ((cw - 3u) & ~3u) + 8u;
@@ -85,7 +85,7 @@ struct Frame {
             if (!nv) pv = make_plane(v, w / 2, ch, 2, pitch16((size_t)(w / 2) * 2), 0, 0x3c, 4);
         } else {
             const u32 need = chroma_need(w, nv);
-            const size_t tail = emu_min_pitch || tight ? 0 : SMR_SURFACE_TAIL;  // (a plane the library owns may be read past a row's end: conv_420_mode)
+            const size_t tail = emu_min_pitch || tight ? 0 : SMR_SURFACE_TAIL;  // (a plane the library owns may be read past a row's end: conv_route)
             py = make_plane(y, w, h, 1, pitch8((size_t)w, 0, tight), tail, 0x5a, 4);
             pu = make_plane(u, w / 2, ch, nv ? 2 : 1, pitch8((size_t)(w / 2) * (nv ? 2 : 1), need, tight), tail, 0xa5, 4);
             if (!nv) pv = make_plane(v, w / 2, ch, 1, pitch8((size_t)(w / 2), need, tight), tail, 0x3c, 4);
@@ -166,7 +166,7 @@ extern "C" int emu_cm_run(const u8 *y, const u8 *u, const u8 *v, int w, int h, i
     return F.finish(out, 0xc0de);
 }
 
-// What a launch of the kind's kernel computes for matrix `matrix`: `n` frames partitioned the way the host does (cv420_plan) over `waves`
+// What a launch of the kind's kernel computes for matrix `matrix`: `n` frames partitioned the way the host does (cv_plan) over `waves`
 // WORKGROUPS, every lane of every wave emulated in turn.  Pointers and ints per frame; output layout per frame as emu_cm_run.
 extern "C" int emu_cm_shares(int n, const u8 *const *ys, const u8 *const *us, const u8 *const *vs, const int *ws, const int *hs, int kind, const int *fulls,
                              const int *rgb12s, int waves, int matrix, int tight, u8 *const *outs) {
@@ -181,7 +181,7 @@ extern "C" int emu_cm_shares(int n, const u8 *const *ys, const u8 *const *us, co
         B.j[i] = F[i].job(fulls[i], matrix);
     }
     u32 grid = (u32)waves;
-    const u32 bands = cv420_plan(B, n, grid * 4u);
+    const u32 bands = cv_plan(B, n);
     if (grid < (bands < 8u ? bands : 8u)) grid = bands < 8u ? bands : 8u;  // (as smr_frames_to_rgba_batch does: every XCD that owns a band runs a workgroup)
     for (u32 blk = 0; blk < grid; blk++)
         for (u32 wv = 0; wv < 4; wv++)

@@ -24,7 +24,7 @@ def emu():
     if not os.path.exists(CLANG):
         pytest.skip("no clang++ to build the emulator with")
     from tests import emu_build
-    lib = emu_build.build("smr_emu_convert", "emu_convert.cpp", ("smr_convert_420.h", "smr_convert_dev.h"))
+    lib = emu_build.build("smr_emu_convert", "emu_convert.cpp", ("smr_convert_420.h", "smr_convert_batch.h", "smr_convert_dev.h"))
     h = C.CDLL(lib)
     h.emu_convert_420.argtypes = [P8, P8, P8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P8]
     h.emu_convert_420_run.argtypes = [P8, P8, P8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P8]
@@ -122,7 +122,7 @@ def test_runs_of_blocks_equal_the_oracle_bit_for_bit(emu, w, h, variant, nb):
 @pytest.mark.parametrize("nv", [0, 1])
 @pytest.mark.parametrize("waves", [1, 3, 8, 9, 13, 64, 1000])
 def test_a_launch_cut_into_equal_shares_writes_the_oracles_bytes(emu, nv, waves):
-    """k_yuv420_to_rgba's partition (cv420_plan + cv420_share): frames of different sizes, ranges and node formats in one launch of `waves`
+    """k_yuv420_to_rgba's partition (cv_plan + cv420_share): frames of different sizes, ranges and node formats in one launch of `waves`
     workgroups — bands of block rows dealt to the eight XCDs, every XCD's units cut into equal contiguous shares per wave: shares that start
     and end anywhere inside a column of blocks, straddle column blocks, bands and frames, more waves than units, XCDs with one workgroup and
     with many — every byte of every frame the oracle's (and none written twice differently: a unit missed or doubled would show)."""
@@ -156,7 +156,7 @@ def test_a_launch_cut_into_equal_shares_writes_the_oracles_bytes(emu, nv, waves)
 def test_converter_never_leaves_its_planes(emu, mode):
     """The memory contract of include/smr.h (smr_surface_wrap): an allocation covers pitch * h bytes and no kernel touches a byte outside it.
     The tests above once more in a child process, with every plane and node texture exactly pitch * h bytes — on the SMALLEST pitch the host
-    code lets through (conv_420_ok: the reach of the last block's dword loads) — ending at (mode 1) or starting behind (mode 2) an unmapped
+    code lets through (conv_route: the reach of the last block's dword loads) — ending at (mode 1) or starting behind (mode 2) an unmapped
     page: a load or store outside the allocation kills the child.  Prefetches included: a run requests nothing behind its last block.
     Mode 3 is the WRITE half of that contract (tests/emu/emu_guard.h): every node texture on the smallest pitch + 32, the whole buffer filled
     from a seeded pattern, the row padding compared after the launch — a 16-byte (RGB12: 12-byte) group store that spilled past a row's last

@@ -31,7 +31,7 @@ def emu():
     if not os.path.exists(CLANG):
         pytest.skip("no clang++ to build the emulator with")
     from tests import emu_build
-    lib = emu_build.build("smr_emu_convert_hi", "emu_convert_hi.cpp", ("smr_convert_hi.h", "smr_convert_420.h", "smr_convert_dev.h", "smr_yuv_fast.h"))
+    lib = emu_build.build("smr_emu_convert_hi", "emu_convert_hi.cpp", ("smr_convert_hi.h", "smr_convert_420.h", "smr_convert_batch.h", "smr_convert_dev.h", "smr_yuv_fast.h"))
     h = C.CDLL(lib)
     h.emu_convert_hi_run.argtypes = [P8, P8, P8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P8]
     PP8, PI = C.POINTER(P8), C.POINTER(C.c_int)
@@ -195,7 +195,7 @@ def test_runs_of_blocks_equal_the_witness_byte_for_byte(emu, w, h, fmt, nb):
 @pytest.mark.parametrize("fmt", ["p010", "planar"])
 @pytest.mark.parametrize("waves", [1, 3, 8, 9, 13, 64, 1000])
 def test_a_launch_cut_into_equal_shares_writes_the_witnesss_bytes(emu, fmt, waves):
-    """k_yuv420_hi_to_rgba's partition (cv420_plan + cvhi_share): five frames of different sizes and node formats in one launch of `waves`
+    """k_yuv420_hi_to_rgba's partition (cv_plan + cvhi_share): five frames of different sizes and node formats in one launch of `waves`
     workgroups — every byte of every frame the witness's (a unit missed or doubled would show)."""
     p010 = fmt == "p010"
     rng = np.random.default_rng(17 * waves + p010)
@@ -224,7 +224,7 @@ def test_a_launch_cut_into_equal_shares_writes_the_witnesss_bytes(emu, fmt, wave
 @pytest.mark.parametrize("mode", [1, 2, 3])
 def test_converter_never_leaves_its_planes(emu, mode):
     """ONE memory contract (include/smr.h, smr_surface_wrap): the tests above once more in a child process with every plane and node texture
-    exactly pitch * h bytes on the SMALLEST pitch conv_hi_mode lets through — the row's own bytes — ending at (mode 1) or starting behind
+    exactly pitch * h bytes on the SMALLEST pitch conv_route lets through — the row's own bytes — ending at (mode 1) or starting behind
     (mode 2) an unmapped page: a load or store outside a plane kills the child, prefetches included.  Mode 3 is the WRITE half
     (tests/emu/emu_guard.h): node textures on the smallest pitch + 32, pre-filled from a seeded pattern, the row padding compared after."""
     if os.environ.get("SMR_EMU_GUARD"):

@@ -38,7 +38,7 @@ def _emu():
     if _HANDLE is None:
         from tests import emu_build
         lib = emu_build.build("smr_emu_convert_hi422", "emu_convert_hi422.cpp",
-                              ("smr_convert_hi422.h", "smr_convert_hi.h", "smr_convert_420.h", "smr_convert_dev.h", "smr_yuv_fast.h"))
+                              ("smr_convert_hi422.h", "smr_convert_hi.h", "smr_convert_420.h", "smr_convert_batch.h", "smr_convert_dev.h", "smr_yuv_fast.h"))
         h = C.CDLL(lib)
         h.emu_convert_hi422_run.argtypes = [P8, P8, P8, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P8]
         PP8, PI = C.POINTER(P8), C.POINTER(C.c_int)
@@ -249,7 +249,7 @@ def _shares(emu, layout, waves, sizes, rgb12, contents):
 @pytest.mark.parametrize("layout", LAYOUTS)
 @pytest.mark.parametrize("waves", [1, 3, 8])
 def test_a_launch_cut_into_equal_shares_writes_each_jobs_own_bytes(emu, layout, waves):
-    """k_yuv422_hi_to_rgba's partition (cv420_plan + cv422_share): five frames of different sizes and node formats in one launch of `waves`
+    """k_yuv422_hi_to_rgba's partition (cv_plan + cv422_share): five frames of different sizes and node formats in one launch of `waves`
     workgroups — every byte of every frame what the job gives alone, and the witness's (a unit missed or doubled would show)."""
     rng = np.random.default_rng(17 * waves + LAYOUT_ID[layout])
     contents = [_content10("noise", w, h, rng) for w, h in SHARE_SIZES]
@@ -284,7 +284,7 @@ def guard_run():
 @pytest.mark.parametrize("mode", [1, 2, 3])
 def test_converter_never_leaves_its_planes(emu, mode, pitch):
     """ONE memory contract (include/smr.h, smr_surface_wrap): guard_run in a child process with every plane and node texture exactly pitch * h
-    bytes — on the SMALLEST pitch conv_hi422_mode lets through, the row's own bytes (tight), and on wide ones (256-byte rows; v210: a capture
+    bytes — on the SMALLEST pitch conv_route lets through, the row's own bytes (tight), and on wide ones (256-byte rows; v210: a capture
     card's stride) — ending at (mode 1) or starting behind (mode 2) an unmapped page: a load or store outside a plane kills the child,
     prefetches included.  Mode 3 is the WRITE half (tests/emu/emu_guard.h): node textures on the smallest pitch + 32, pre-filled from a seeded
     pattern, the row padding compared after."""

@@ -30,7 +30,7 @@ def _emu():
     if _HANDLE is None:
         from tests import emu_build
         lib = emu_build.build("smr_emu_convert_matrix", "emu_convert_matrix.cpp",
-                              ("smr_convert_hi422.h", "smr_convert_hi.h", "smr_convert_420.h", "smr_convert_dev.h", "smr_yuv_fast.h", "smr_frame_formats.h"))
+                              ("smr_convert_hi422.h", "smr_convert_hi.h", "smr_convert_420.h", "smr_convert_batch.h", "smr_convert_dev.h", "smr_yuv_fast.h", "smr_frame_formats.h"))
         h = C.CDLL(lib)
         i = C.c_int
         h.emu_cm_run.argtypes = [P8, P8, P8, i, i, i, i, i, i, i, i, P8]
@@ -136,7 +136,7 @@ MIXED = [(132, 74), (8, 2), (260, 10), (64, 36), (12, 4)]
 @pytest.mark.parametrize("matrix", MATRICES)
 @pytest.mark.parametrize("variant", [v for v in VARIANTS if v != "j420"])
 def test_multi_job_launch_of_mixed_sizes(emu, variant, matrix, waves):
-    """Five frames of mixed sizes and node formats in one launch, cut by the host's own cv420_plan; planar 4:2:0 mixes both ranges."""
+    """Five frames of mixed sizes and node formats in one launch, cut by the host's own cv_plan; planar 4:2:0 mixes both ranges."""
     contents = [_planes(variant, w, h, "noise", 100 + i) for i, (w, h) in enumerate(MIXED)]
     rgb12s = [1, 0, 1, 0, 1]
     fulls = [0, 1, 0, 1, 0] if variant == "420" else None

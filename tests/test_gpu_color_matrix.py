@@ -104,7 +104,7 @@ def _device_plane(torch, arr2d, pitch):
 @pytest.mark.parametrize("matrix", MATRICES)
 @pytest.mark.parametrize("name", ["420", "j420", "nv12"])
 def test_a_wrapped_frame_with_tight_rows_gives_the_witnesss_bytes(ctx, hip, name, matrix):
-    """A frame over caller memory on the tightest pitch smr_surface_wrap admits: conv_420_mode sends it to k_yuv420_to_rgba_tight.  What is checked
+    """A frame over caller memory on the tightest pitch smr_surface_wrap admits: conv_route sends it to k_yuv420_to_rgba_tight.  What is checked
     is the bytes and that ONE block-converter launch made them; the counter is shared with the plain kernel, so which instantiation ran is not
     observable here (tests/test_emu_convert_matrix.py runs the tight build of each matrix by name, guard pages behind its planes)."""
     torch = pytest.importorskip("torch")
@@ -221,6 +221,46 @@ def test_a_batch_that_mixes_matrices(ctx, hip):
         assert np.array_equal(d.download(), single[m]), cm.NAMES[m]
     assert not np.array_equal(single[cm.BT709], single[cm.BT601]) and not np.array_equal(single[cm.BT709], single[cm.BT2020_NCL])
     assert not np.array_equal(single[cm.BT601], single[cm.BT2020_NCL])
+
+
+# what the commit before the converter's routes became one classifier and one kernel table launched for test_a_batch_that_takes_every_route's
+# batch (measured there, on the device): the refactor changes no launch
+PARENT_LAUNCHES_OF_THE_EVERY_ROUTE_BATCH = {"frame_to_rgba": 13, "frame_to_rgba_420": 11}
+
+
+def test_a_batch_that_takes_every_route(ctx, hip):
+    """One ingest_resample_batch call whose frames take every converter route at once: a 16 x 4 frame of each block-kernel format (J420 and NV12
+    tagged BT.601), a wrapped NV12 frame with tight rows (BT.2020: the tight kernel), a 10 x 4 planar 4:2:0 frame (the 4 x 2 batch kernel), a
+    7 x 3 one (general) and seventeen 8 x 4 NV12 frames — one queue fills and is launched mid-batch (8 x 2 has no two-pass plan: 8 x 4 is the
+    smallest frame the resampler's node route takes).  Every destination is byte-equal to the same frame through ingest_resample alone, and the
+    two converter counters move as they did before the refactor."""
+    torch = pytest.importorskip("torch")
+    specs = [(BLOCK_FORMATS[n], m, 16, 4) for n, m in (("420", cm.BT709), ("j420", cm.BT601), ("nv12", cm.BT601), ("p010", cm.BT709), ("420p10", cm.BT709),
+                                                      ("422p10", cm.BT709), ("p210", cm.BT709), ("v210", cm.BT709))]
+    specs += [(cm.PLANAR_YUV420, cm.BT709, 10, 4), (cm.PLANAR_YUV420, cm.BT709, 7, 3)] + [(cm.NV12, cm.BT709, 8, 4)] * 17
+    keep, frames = [], []
+    for i, (base, m, w, h) in enumerate(specs):
+        frames.append(_frame(ctx, hip, base, m, w, h, cm.noise_planes(base, w, h, 500 + i))[0])
+    planes = cm.noise_planes(cm.NV12, 16, 4, 499)  # the wrapped frame: rows that fill their pitch
+    rows = [np.ascontiguousarray(p).view(np.uint8).reshape(p.shape[0], -1) for p in planes]
+    keep = [_device_plane(torch, r, r.shape[1]) for r in rows]
+    frames.append(ctx.wrapped_frame(hip.frame_format(cm.NV12, cm.BT2020_NCL), 16, 4, [(b.data_ptr(), r.shape[1]) for b, r in zip(keep, rows)]))
+    sizes = [(f.w, f.h, f.w * 3 // 4, f.h * 3 // 4) for f in frames]
+    crops = [(0.0, 0.0, float(w), float(h)) for w, h, _, _ in sizes]
+    single, kinds1 = [], []
+    for f, c, (_, _, dw, dh) in zip(frames, crops, sizes):
+        dst = ctx.surface(dw, dh)
+        kinds1.append(ctx.ingest_resample(f, c, dst))
+        single.append(dst.download())
+    dsts = [ctx.surface(dw, dh) for _, _, dw, dh in sizes]
+    before = ctx.kernel_launches()
+    kinds = ctx.ingest_resample_batch(frames, crops, dsts)
+    ran = _ran(ctx, before)
+    print("every-route batch:", {k: ran[k] for k in PARENT_LAUNCHES_OF_THE_EVERY_ROUTE_BATCH}, "kinds", kinds)
+    assert kinds == kinds1 and all(k > 0 for k in kinds), (kinds, kinds1)
+    for i, (d, s) in enumerate(zip(dsts, single)):
+        assert np.array_equal(d.download(), s), (i, specs[i] if i < len(specs) else "wrapped nv12", _diff(d.download(), s))
+    assert {k: ran[k] for k in PARENT_LAUNCHES_OF_THE_EVERY_ROUTE_BATCH} == PARENT_LAUNCHES_OF_THE_EVERY_ROUTE_BATCH, ran
 
 
 @pytest.mark.parametrize("iw,ih,dw,dh", [(64, 36, 40, 22), (256, 144, 96, 54), (384, 216, 256, 144)])
