@@ -16,8 +16,10 @@ the oracle on that path.  The table below is the map of the fast paths and of wh
                Windows too wide for a column pair (scales above ~3.2: 9 or 10 k-steps) are worked one 16-column tile per wave
                (axis 4 bands) on the node-texture routes.
 * `general`    smr_frame_to_rgba + smr_resample (box pre-reduction and Lanczos pass kernels, f32): nothing of this table any more —
-               what still takes it are resample targets smaller than the kernel's minimum source (8 x 2) and degenerate plans.  Nothing falls to the one-launch f32 kernel
-               (k_ingest_resample) any more unless SMR_INGEST_VALU_F32 asks for it.
+               what still takes it are sources (after the box reduction) smaller than the kernel's minimum of 8 x 2, single-axis plans behind
+               a box level and degenerate plans.  Nothing of this table falls to the one-launch f32 kernel (k_ingest_resample) unless
+               SMR_INGEST_VALU_F32 asks for it; by default it still gets the 4:2:0 frames under 8 x 2 whose plan is two-pass, horizontal
+               first, without a box level (4 x 2 -> 5 x 3: tests/test_gpu_small_tiles.py walks these sizes and records the routes).
 """
 import numpy as np
 import pytest
