@@ -65,6 +65,25 @@ typedef enum smr_frame_format {
     SMR_FRAME_PLANAR_YUV422 = 1,
     SMR_FRAME_PLANAR_YUV444 = 2,
     SMR_FRAME_PLANAR_YUVJ420 = 3,
+    /* 8-bit packed 4:2:2, one SMR_PX_RGBA8 plane of (w / 2) x h texels: a texel holds two pixels, U Y0 V Y1 (UYVY, the `2vuy` of SDI playout
+     * cards) or Y0 U Y1 V (YUYV / YUY2, what V4L2 output and loopback devices, virtual cameras and most capture-style APIs take), in memory order.
+     * As INPUTS: interleaved_{uyvy,yuyv}_to_rgba.wgsl, any width.
+     * As OUTPUTS (smr_rgba_to_frame, smr_frame_fill_black, smr_render_layouts' `out`, a renderer's output_format; the reference's
+     * OutputFrameFormat has no packed variant: a host opts in by passing the format): BT.709, limited range and 8-bit like every other
+     * output, and nothing new numerically — for an even width the frame's bytes are an interleave of the planes SMR_FRAME_PLANAR_YUV422
+     * output gives for the same node texture: texel j of row y holds U[y][j] Y[y][2j] V[y][j] Y[y][2j+1] (UYVY) or Y[y][2j] U[y][j]
+     * Y[y][2j+1] V[y][j] (YUYV); Y is rgba_to_yuv.wgsl's luma of the pixel, U and V its chroma of the pair's horizontal mean
+     * a * .5 + b * .5, each channel byte / 255 first; range compression and the unorm8 store unchanged.
+     *   width   even and at least 2 (a packed 4:2:2 raster has no odd width): an odd-width OUTPUT frame is SMR_ERR_INVALID at every output
+     *           entry point ("... needs an even width"), refused before anything is launched; for the renderer the previous scene stays
+     *           active.  Input frames of odd width keep working as they do.
+     *   height  any, from 1.
+     *   black   smr_frame_fill_black and an empty output give Y = 16, U = V = 128: texels 80 10 80 10 (UYVY) / 10 80 10 80 (YUYV).
+     *   still refused, as for every output: a matrix tag, the 10-bit formats (v210 included), a bit above bit 11, a missing plane, a plane
+     *           that is not SMR_PX_RGBA8 of (w / 2) x h.
+     *   memory  smr_surface_wrap's write contract holds for a packed destination: every row gets its w * 2 bytes and no other byte is written;
+     *           stores wider than a texel are used only where the plane's base and pitch allow them (8-byte alignment for the compositor's
+     *           own store, otherwise the frame is composed as RGBA8 and converted in one more launch: the same bytes). */
     SMR_FRAME_UYVY422 = 4,
     SMR_FRAME_YUYV422 = 5,
     SMR_FRAME_NV12 = 6,
@@ -348,9 +367,12 @@ SMR_API int smr_remove_premultiplied_alpha(smr_ctx *ctx, const smr_surface *src,
 
 /* ---- a11: read_outputs (render_loop.rs:59-230) -------------------------------------
  * RgbaToYuvConverter::convert (format/rgba_to_yuv.rs:67-117) for planar 420/422/444,
- * RgbaToNv12Converter::convert (format/rgba_to_nv12.rs:54-82) for NV12. */
+ * RgbaToNv12Converter::convert (format/rgba_to_nv12.rs:54-82) for NV12; SMR_FRAME_RGBA is a copy; SMR_FRAME_UYVY422 / SMR_FRAME_YUYV422 (even
+ * widths; this library's own, see smr_frame_format) are the planar 4:2:2 planes interleaved, one launch, any height.  The 10-bit formats
+ * and a format with a matrix tag are refused. */
 SMR_API int smr_rgba_to_frame(smr_ctx *ctx, const smr_surface *node, const smr_frame *out);
-/* PlanarYuvTextures::fill_with_color(BLACK) (wgpu/texture/planar_yuv.rs:190-202) */
+/* PlanarYuvTextures::fill_with_color(BLACK) (wgpu/texture/planar_yuv.rs:190-202): Y = 16, U = V = 128 in every plane of a planar / NV12
+ * frame and in every texel of a packed 4:2:2 frame (even widths); zeros for SMR_FRAME_RGBA.  Other formats are refused. */
 SMR_API int smr_frame_fill_black(smr_ctx *ctx, const smr_frame *out);
 
 /* ---- a7/a8: resampler (layout/resampler.rs) ---------------------------------------- */
@@ -871,7 +893,10 @@ SMR_API int smr_renderer_register_shader_program(smr_renderer *r, const char *sh
  * unknown shader ids, (with a font book) Text nodes no run can be made of (empty font book, text that is not UTF-8, absurd sizes), and an
  * SVG asset's raster that could not be made (the rasteriser said no, or an allocation failed: "SVG image assets" above).  One
  * failure is reported AFTER the new scene is in place: a device allocation that fails while the output's frames or a Text node's surface are
- * created (SMR_ERR_OOM): the new scene is active, the nodes that could not be drawn render transparent. */
+ * created (SMR_ERR_OOM): the new scene is active, the nodes that could not be drawn render transparent.
+ * output_format: SMR_FRAME_PLANAR_YUV420 / _YUV422 / _YUV444, SMR_FRAME_NV12, SMR_FRAME_RGBA, or packed 4:2:2 — SMR_FRAME_UYVY422 /
+ * SMR_FRAME_YUYV422, an even `width` only (see smr_frame_format).  Anything else — a 10-bit format, a matrix tag, an odd width of a packed
+ * format — is refused like a scene error: the previous scene stays active. */
 SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, uint32_t width, uint32_t height, uint32_t output_format,
                                       const char *scene_json);
 SMR_API int smr_renderer_unregister_output(smr_renderer *r, const char *output_id);
@@ -935,7 +960,9 @@ SMR_API int smr_renderer_sync(smr_renderer *r);
  *      SMR_KERNEL_INGEST_MFMA_WG, counts SMR_KERNEL_FRAME_TO_RGBA_420.  smr_text_params moved in front of the font-book entry points.  The
  *      SMR_CONVERT_GENERAL / SMR_DISABLE_FUSED / SMR_COMPOSE_SELECT environment knobs are smr_ctx_set_option options in a product build
  *      (the environment is read by laboratory builds only).
- *      Added since, without a new version (additions only: nothing a version-2 host calls changed) — the latest first: input colour
+ *      Added since, without a new version (additions only: nothing a version-2 host calls changed) — the latest first: packed 4:2:2
+ *      OUTPUT frames (SMR_FRAME_UYVY422 / SMR_FRAME_YUYV422 where a frame is an output: two values every version-2 host was refused; no new
+ *      symbol, struct, option or kernel counter slot, no frame that was accepted before is converted differently); input colour
  *      matrices (smr_color_matrix, SMR_FRAME_WITH_MATRIX / _BASE_FORMAT / _MATRIX: bits 8 - 11 of smr_frame.format, which every version-2
  *      host leaves zero = BT.709; no struct changed, no kernel counter slot was added, no untagged frame converts differently); then, oldest
  *      first: SMR_KERNEL_MOVE_RECTS (counter slot 8),

@@ -1448,9 +1448,11 @@ SMR_API int smr_renderer_update_scene(smr_renderer *r, const char *output_id, ui
         return fail(r, -1, frame_format_tag_error(output_format) ? "smr_renderer_update_scene: output format has bits outside a colour matrix the library knows; and an output format carries no colour matrix at all"
                                                                   : "smr_renderer_update_scene: output format carries a colour matrix: outputs are BT.709, a matrix applies to input frames only");
     if (output_format != SMR_FRAME_PLANAR_YUV420 && output_format != SMR_FRAME_PLANAR_YUV422 && output_format != SMR_FRAME_PLANAR_YUV444 &&
-        output_format != SMR_FRAME_NV12 && output_format != SMR_FRAME_RGBA)
-        return fail(r, -1, frame_format_is_hi_depth(output_format) ? "smr_renderer_update_scene: the 10-bit frame formats are input only; output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12 or RGBA"
-                                                                   : "smr_renderer_update_scene: output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12 or RGBA");
+        output_format != SMR_FRAME_NV12 && output_format != SMR_FRAME_RGBA && !frame_format_is_packed_422(output_format))
+        return fail(r, -1, frame_format_is_hi_depth(output_format) ? "smr_renderer_update_scene: the 10-bit frame formats are input only; output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12, UYVY, YUYV or RGBA"
+                                                                   : "smr_renderer_update_scene: output format must be planar YUV 4:2:0 / 4:2:2 / 4:4:4, NV12, UYVY, YUYV or RGBA");
+    if (frame_format_is_packed_422(output_format) && width % 2 != 0)
+        return fail(r, -1, "smr_renderer_update_scene: " SMR_PACKED_OUTPUT_WIDTH_MSG);
     Output &o = r->outputs[output_id];
     for (auto &kv : r->images) o.scene.register_image(kv.first, (float)kv.second.w, (float)kv.second.h);
     for (auto &kv : r->web) o.scene.register_web_renderer(kv.first, (float)kv.second.w, (float)kv.second.h);

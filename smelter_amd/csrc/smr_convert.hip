@@ -523,6 +523,52 @@ __global__ __launch_bounds__(BLOCK) void k_rgba_to_planes(SurfView src, SurfView
     }
 }
 
+// rgba_to_yuv.wgsl's passes for a packed 4:2:2 frame (include/smr.h: the planes of the planar 4:2:2 output, interleaved): a thread owns four
+// pixels of one row — two texels of the frame's plane — or, in the last group of a width with w % 4 == 2, two pixels and one texel.  The
+// values are k_rgba_to_planes' for sx = 1, sy = 0, operation for operation: channels are byte / 255 (unorm_of_byte), the chroma of a pair
+// comes from a * .5 + b * .5 (a sample exactly between two texels; nothing depends on the frame's size: any height, any even width), planes
+// and store are yuv_byte.  ORDER 0: U Y0 V Y1 (UYVY) | 1: Y0 U Y1 V (YUYV).
+// ld16 / st8 (uniform): the node's base and pitch take 16-byte loads / the plane's take 8-byte stores; dwords otherwise (both are RGBA8
+// surfaces: texel-aligned at least).
+template <int ORDER>
+__global__ __launch_bounds__(BLOCK) void k_rgba_to_packed422(SurfView src, SurfView dst, int ld16, int st8) {
+    const int g = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int w = src.w;
+    if (4 * g >= w || y >= src.h) return;
+    const bool whole = 4 * g + 3 < w;
+    const u8 *row = src.ptr + ((size_t)y * src.pitch + 16u * (size_t)g);
+    u32 t[4];
+    if (whole && ld16) {
+        const uint4 q = *(const uint4 *)row;
+        t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) t[i] = ((const u32 *)row)[whole ? i : (i & 1)];
+    }
+    u32 tex[2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        float c[2][3];
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            c[i][0] = unorm_of_byte(t[2 * k + i] & 0xffu); c[i][1] = unorm_of_byte((t[2 * k + i] >> 8) & 0xffu); c[i][2] = unorm_of_byte((t[2 * k + i] >> 16) & 0xffu);
+        }
+        const u32 y0 = yuv_byte(c[0][0], c[0][1], c[0][2], 0), y1 = yuv_byte(c[1][0], c[1][1], c[1][2], 0);
+        float m[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) m[ch] = c[0][ch] * 0.5f + c[1][ch] * 0.5f;
+        const u32 u = yuv_byte(m[0], m[1], m[2], 1), v = yuv_byte(m[0], m[1], m[2], 2);
+        tex[k] = ORDER == 0 ? u | (y0 << 8) | (v << 16) | (y1 << 24) : y0 | (u << 8) | (y1 << 16) | (v << 24);
+    }
+    u8 *d = dst.ptr + ((size_t)y * dst.pitch + 8u * (size_t)g);
+    if (whole && st8) {
+        *(uint2 *)d = make_uint2(tex[0], tex[1]);
+    } else {
+        *(u32 *)d = tex[0];
+        if (whole) ((u32 *)d)[1] = tex[1];
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_fill_bytes(SurfView p, int row_bytes, u32 value4) {
     const int x = (blockIdx.x * BLOCK + threadIdx.x) * 4;
     const int y = blockIdx.y;
@@ -783,11 +829,24 @@ int smr_rgba_to_frame(smr_ctx *ctx, const smr_surface *node, const smr_frame *ou
     if (int rc = smr_validate_frame(ctx, out, "smr_rgba_to_frame")) return rc;
     if (frame_matrix(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: frame format 0x%x carries a colour matrix: outputs are BT.709, a matrix applies to input frames only", out->format);
     if (frame_format_is_hi_depth(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: frame format %u (10-bit) is input only", out->format);
+    if (frame_format_is_packed_422(out->format) && out->width % 2 != 0)
+        return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: %ux%u: " SMR_PACKED_OUTPUT_WIDTH_MSG, out->width, out->height);
     StageScope scope(ctx, SMR_STAGE_OUTPUT);
     const int w = (int)out->width, h = (int)out->height;
     SurfView src = view_of(node);
     int cw, ch;
     switch (out->format) {
+    case SMR_FRAME_UYVY422:
+    case SMR_FRAME_YUYV422: {
+        // one launch whatever SMR_OPT_CONVERT_IMPL says: the kernel is the general one (any height, any even width, texel-aligned surfaces)
+        const smr_surface *p = out->planes[0];
+        const int ld16 = (((uintptr_t)src.ptr) & 15) == 0 && (src.pitch & 15u) == 0, st8 = (((uintptr_t)p->ptr) & 7) == 0 && (p->pitch & 7u) == 0;
+        const dim3 grid((unsigned)((w + 255) / 256), (unsigned)((h + 3) / 4), 1);
+        if (out->format == SMR_FRAME_UYVY422) hipLaunchKernelGGL(k_rgba_to_packed422<0>, grid, dim3(BLOCK), 0, ctx->stream, src, view_of(p), ld16, st8);
+        else hipLaunchKernelGGL(k_rgba_to_packed422<1>, grid, dim3(BLOCK), 0, ctx->stream, src, view_of(p), ld16, st8);
+        SMR_HIP(ctx, hipGetLastError());
+        return SMR_OK;
+    }
     case SMR_FRAME_RGBA:
         // OutputTexture::Rgba8UnormWgpuTexture (render_loop.rs:81-103): the frame is a clone of the root node's texture, as it is
         SMR_HIP(ctx, hipMemcpy2DAsync(out->planes[0]->ptr, out->planes[0]->pitch, node->ptr, node->pitch, (size_t)w * 4, (size_t)h,
@@ -798,7 +857,7 @@ int smr_rgba_to_frame(smr_ctx *ctx, const smr_surface *node, const smr_frame *ou
     case SMR_FRAME_PLANAR_YUV444: cw = w; ch = h; break;
     case SMR_FRAME_NV12: cw = w / 2; ch = h / 2; break;
     default:
-        // output_texture.rs:26-38 only offers 420/422/444 planar, RGBA and NV12 outputs
+        // output_texture.rs:26-38 only offers 420/422/444 planar, RGBA and NV12 outputs; packed 4:2:2 (above) is this library's own
         return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: unsupported output frame format %u", out->format);
     }
     if (!out->planes[0] || !out->planes[1]) return smr_fail(ctx, SMR_ERR_INVALID, "smr_rgba_to_frame: missing planes");
@@ -838,6 +897,8 @@ int smr_frame_fill_black(smr_ctx *ctx, const smr_frame *out) {
     if (!ctx || !out || !out->planes[0]) return SMR_ERR_INVALID;
     if (frame_matrix(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_fill_black: frame format 0x%x carries a colour matrix: outputs are BT.709, a matrix applies to input frames only", out->format);
     if (frame_format_is_hi_depth(out->format)) return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_fill_black: frame format %u (10-bit) is input only", out->format);
+    if (frame_format_is_packed_422(out->format) && out->width % 2 != 0)
+        return smr_fail(ctx, SMR_ERR_INVALID, "smr_frame_fill_black: %ux%u: " SMR_PACKED_OUTPUT_WIDTH_MSG, out->width, out->height);
     // RGBColor::BLACK.to_yuv(), smelter-render/src/scene/types.rs:28-41
     const float y = (0.0f * 0.85882354f) + (16.0f / 255.0f);
     const float c = ((0.0f + 0.5f) * 0.8784314f) + (16.0f / 255.0f);
@@ -845,6 +906,14 @@ int smr_frame_fill_black(smr_ctx *ctx, const smr_frame *out) {
     StageScope scope(ctx, SMR_STAGE_OUTPUT);
     if (out->format == SMR_FRAME_RGBA) {  // render_loop.rs:140-158: a fresh (all-zero) texture when the root is empty
         SMR_HIP(ctx, hipMemset2DAsync(out->planes[0]->ptr, out->planes[0]->pitch, 0, (size_t)out->width * 4, out->height, ctx->stream));
+        return SMR_OK;
+    }
+    if (frame_format_is_packed_422(out->format)) {  // every texel U Y V Y / Y U Y V of black: the plane's rows hold w * 2 bytes
+        const smr_surface *s = out->planes[0];
+        const int row_bytes = (int)out->width * 2;
+        hipLaunchKernelGGL(k_fill_bytes, grid_px((row_bytes + 3) / 4, (int)s->h), dim3(BLOCK), 0, ctx->stream, view_of(s), row_bytes,
+                           out->format == SMR_FRAME_UYVY422 ? cb * 0x00010001u | yb * 0x01000100u : yb * 0x00010001u | cb * 0x01000100u);
+        SMR_HIP(ctx, hipGetLastError());
         return SMR_OK;
     }
     for (int i = 0; i < 3; i++) {

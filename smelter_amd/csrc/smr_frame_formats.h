@@ -39,6 +39,14 @@ static inline bool frame_format_is_hi_depth_422(uint32_t format) {
     return format == SMR_FRAME_PLANAR_YUV422P10 || format == SMR_FRAME_P210 || format == SMR_FRAME_V210;
 }
 
+// 8-bit packed 4:2:2, one RGBA8 plane of (w / 2) x h texels: an input of any width, an output of an even width only (include/smr.h) —
+// what every output entry point says about the other widths
+static inline bool frame_format_is_packed_422(uint32_t format) {
+    format = frame_base_format(format);
+    return format == SMR_FRAME_UYVY422 || format == SMR_FRAME_YUYV422;
+}
+#define SMR_PACKED_OUTPUT_WIDTH_MSG "a packed 4:2:2 output (UYVY / YUYV) needs an even width: a texel holds two pixels"
+
 // "this frame format is opaque Y'CbCr": every texel of its node texture has alpha 1 (planar_yuv_to_rgba.wgsl:57) — what the opaque routes
 // (RGB12 nodes, tiles without alpha, opaque layers) ask.  The formats by name: a new enum value is not opaque until it is listed here.
 static inline bool frame_format_is_opaque_ycbcr(uint32_t format) {

@@ -21,7 +21,7 @@
 // that cannot act on the operands at hand, layers an opaque layer overwrites) — tests/test_gpu_fused.py checks fused ==
 // pass-per-launch bit for bit; the matrix-core resampler stays within 1 LSB of the f32 passes on the same node texture.
 // Anything the fused kernels do not cover (single-pass plans, box pre-reduction, packed inputs, odd
-// output sizes, 4:2:2 / 4:4:4 outputs) falls back to the general kernels of smr_convert / smr_resample / smr_layout per
+// output sizes, planar 4:2:2 / 4:4:4 outputs) falls back to the general kernels of smr_convert / smr_resample / smr_layout per
 // layout — never to the CPU.
 #include "smr_fused_compose.h"
 #include "smr_fused_ingest.h"
@@ -88,6 +88,8 @@ extern "C" int smr_render_layouts(smr_ctx *ctx, const smr_layout *layouts, uint3
         return smr_fail(ctx, SMR_ERR_INVALID, "smr_render_layouts: out_rgba must be RGBA8 %ux%u", out_w, out_h);
     if (out)
         if (int rc = smr_validate_frame(ctx, out, "smr_render_layouts (output)")) return rc;
+    if (out && frame_format_is_packed_422(out->format) && !frame_matrix(out->format) && out_w % 2 != 0)  // (a tagged output: smr_rgba_to_frame's refusal, as ever)
+        return smr_fail(ctx, SMR_ERR_INVALID, "smr_render_layouts: %ux%u: " SMR_PACKED_OUTPUT_WIDTH_MSG, out_w, out_h);
     if (n > ctx->max_layouts) n = ctx->max_layouts;
     if (n > SMR_SLOT_MAX_LAYOUTS) n = (uint32_t)SMR_SLOT_MAX_LAYOUTS;  // (the packer draws no more than MAX_LAYOUT_WORDS * 32 = 1024 anyway; every per-layout scratch slot stays in its range)
     if (n_sources > SMR_SLOT_MAX_SOURCES) return smr_fail(ctx, SMR_ERR_INVALID, "smr_render_layouts: too many sources");
@@ -413,15 +415,19 @@ extern "C" int smr_render_layouts(smr_ctx *ctx, const smr_layout *layouts, uint3
     const bool big_list = packed.n > B_MAX_LAYOUTS || packed.n_masks > B_MAX_MASKS;  // read in place instead of from an LDS copy
     const bool fuse_yuv = fits_b && out && !out_rgba && (out->format == SMR_FRAME_PLANAR_YUV420 || out->format == SMR_FRAME_NV12) &&
                           out->planes[0] && out->planes[1] && (out->format == SMR_FRAME_NV12 || out->planes[2]);
-    // an RGBA8 target: a node's texture (out_rgba), or — for the output formats wave B does not write itself (4:2:2, 4:4:4, full-range
+    // a packed 4:2:2 output (UYVY / YUYV): wave B stores its texels itself where the plane takes 8-byte stores (the library's own planes
+    // always: their pitch is a multiple of 256); an under-aligned wrapped plane goes the way of planar 4:2:2 below, to the same bytes
+    const bool fuse_packed = fits_b && out && !out_rgba && (out->format == SMR_FRAME_UYVY422 || out->format == SMR_FRAME_YUYV422) && out->planes[0] &&
+                             ((((uintptr_t)out->planes[0]->ptr) | out->planes[0]->pitch) & 7u) == 0;
+    // an RGBA8 target: a node's texture (out_rgba), or — for the output formats wave B does not write itself (planar 4:2:2, 4:4:4, full-range
     // 4:2:0, RGBA) — a scratch surface the output converter then reads (smr_rgba_to_frame): the same compositor kernel either way
     smr_surface *rgba_target = out_rgba;
-    if (!rgba_target && fits_b && !fuse_yuv) {
+    if (!rgba_target && fits_b && !fuse_yuv && !fuse_packed) {
         rgba_target = smr_cached_surface(ctx, SLOT_TARGET, out_w, out_h, SMR_PX_RGBA8);
         if (!rgba_target) return SMR_ERR_OOM;
     }
-    const bool fuse_rgba = fits_b && !fuse_yuv && rgba_target && (((uintptr_t)rgba_target->ptr) % 16 == 0) && (rgba_target->pitch % 16 == 0);
-    const bool fuse_out = fuse_yuv || fuse_rgba;
+    const bool fuse_rgba = fits_b && !fuse_yuv && !fuse_packed && rgba_target && (((uintptr_t)rgba_target->ptr) % 16 == 0) && (rgba_target->pitch % 16 == 0);
+    const bool fuse_out = fuse_yuv || fuse_rgba || fuse_packed;  // (SMR_OPT_DIRECT_OUTPUT declines packed outputs: direct_mask stays 0 below)
 
     // ---- tile classes (k_classify_tiles): kept while a layout list repeats (a scene at rest; a few lists per context, so a
     //      nested node and the root do not evict each other), recomputed when it changes.
@@ -617,6 +623,9 @@ extern "C" int smr_render_layouts(smr_ctx *ctx, const smr_layout *layouts, uint3
         if (fuse_rgba) {
             p0 = p1 = p2 = view_of(rgba_target);
             nv = 2;
+        } else if (fuse_packed) {
+            p0 = p1 = p2 = view_of(out->planes[0]);
+            nv = out->format == SMR_FRAME_UYVY422 ? 3 : 4;
         } else {
             p0 = view_of(out->planes[0]); p1 = view_of(out->planes[1]);
             nv = out->format == SMR_FRAME_NV12 ? 1 : 0;
@@ -624,9 +633,11 @@ extern "C" int smr_render_layouts(smr_ctx *ctx, const smr_layout *layouts, uint3
         }
         typedef void (*ComposeKernel)(SurfView, SurfView, SurfView, int, int, const DevLayout *, const DevMask *, int, int, int, const float *, int, int,
                                       const TileClass *, const TileList *, int, int);
-        static const ComposeKernel kernels[3][2] = {{k_compose_output<0, false>, k_compose_output<0, true>},
+        static const ComposeKernel kernels[5][2] = {{k_compose_output<0, false>, k_compose_output<0, true>},
                                                     {k_compose_output<1, false>, k_compose_output<1, true>},
-                                                    {k_compose_output<2, false>, k_compose_output<2, true>}};
+                                                    {k_compose_output<2, false>, k_compose_output<2, true>},
+                                                    {k_compose_output<3, false>, k_compose_output<3, true>},
+                                                    {k_compose_output<4, false>, k_compose_output<4, true>}};
         hipLaunchKernelGGL(kernels[nv][big_list ? 1 : 0], grid, dim3(256), 0, ctx->stream, p0, p1, p2, (int)out_w, (int)out_h, packed.layouts, packed.masks,
                            packed.n, packed.n_masks, flags, ctx->d_tables, (int)b_tiles_x, (int)b_tiles, tc, full, (int)n_banded, cm->counter);
         SMR_HIP(ctx, hipGetLastError());

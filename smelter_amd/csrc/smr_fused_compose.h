@@ -415,6 +415,116 @@ __device__ __forceinline__ void yuv_block_repair(const u32 (&acc)[8], u32 &yrow0
     }
 }
 
+// ---- packed 4:2:2 outputs (NV 3: UYVY, NV 4: YUYV; include/smr.h): a lane's 4 x 2 block is two texels in each of two rows — per row four Y',
+// and the Cb and Cr of its two horizontal pixel pairs.  Luma is the fast path of the planar stores (yuvfast::convert<0>), chroma its pair twin
+// (convert422: the pair's byte sums, the / 2 of the mean folded in; tools/check_yuv_fast_422.cpp proves it over the complete domain), sixteen
+// guard flags per block behind ONE branch.  All of it is reached from store_yuv_block only behind `NV >= 3`: the builds for NV 0 .. 2 hold
+// none of it.
+
+// The cold half, yuv_block_repair's twin for two pairs per row: the flagged values again with the reference sequence (unorm_of_byte, the 4:2:2
+// chroma sample a * .5 + b * .5 of k_rgba_to_planes, yuv_byte).  uv0 / uv1: a row's chroma bytes U(pair 0) U(pair 1) V(pair 0) V(pair 1).
+__device__ __forceinline__ void yuv_block_repair_422(const u32 (&acc)[8], u32 &yrow0, u32 &yrow1, u32 &uv0, u32 &uv1) {
+    u32 px[8];
+    float r[8], g[8], b[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        px[k] = acc[k];
+        B_KEEP_IN_LOOP(px[k]);
+        r[k] = unorm_of_byte(px[k] & 0xffu);
+        g[k] = unorm_of_byte((px[k] >> 8) & 0xffu);
+        b[k] = unorm_of_byte((px[k] >> 16) & 0xffu);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        bool f;
+        (void)yuvfast::convert<0>((float)(px[k] & 0xffu), (float)((px[k] >> 8) & 0xffu), (float)((px[k] >> 16) & 0xffu), &f);
+        const u32 exact = yuv_byte(r[k], g[k], b[k], 0), sh = 8u * (u32)(k & 3);
+        u32 &row = k < 4 ? yrow0 : yrow1;
+        row = f ? ((row & ~(0xffu << sh)) | (exact << sh)) : row;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {  // pair q & 1 of row q >> 1
+        const int a = 4 * (q >> 1) + 2 * (q & 1);
+        float sum[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) sum[ch] = (float)((px[a] >> (8 * ch)) & 0xffu) + (float)((px[a + 1] >> (8 * ch)) & 0xffu);
+        bool f1, f2;
+        (void)yuvfast::convert422<1>(sum[0], sum[1], sum[2], &f1);
+        (void)yuvfast::convert422<2>(sum[0], sum[1], sum[2], &f2);
+        const float mr = r[a] * 0.5f + r[a + 1] * 0.5f, mg = g[a] * 0.5f + g[a + 1] * 0.5f, mb = b[a] * 0.5f + b[a + 1] * 0.5f;
+        const u32 eu = yuv_byte(mr, mg, mb, 1), ev = yuv_byte(mr, mg, mb, 2), su = 8u * (u32)(q & 1), sv = su + 16u;
+        u32 &uv = q < 2 ? uv0 : uv1;
+        uv = f1 ? ((uv & ~(0xffu << su)) | (eu << su)) : uv;
+        uv = f2 ? ((uv & ~(0xffu << sv)) | (ev << sv)) : uv;
+    }
+}
+
+// Texel `j` (0, 1) of a block row: y4 = its four Y' bytes, uv = U0 U1 V0 V1.  ORDER 3: U Y V Y, 4: Y U Y V — byte moves.
+template <int NV>
+__device__ __forceinline__ u32 packed422_texel(u32 y4, u32 uv, int j) {
+    const u32 ya = (y4 >> (16 * j)) & 0xffu, yb = (y4 >> (16 * j + 8)) & 0xffu, u = (uv >> (8 * j)) & 0xffu, v = (uv >> (16 + 8 * j)) & 0xffu;
+    return NV == 3 ? u | (ya << 8) | (v << 16) | (yb << 24) : ya | (u << 8) | (yb << 16) | (v << 24);
+}
+
+// Whether a packed plane takes the paired stores (16 bytes of one row per lane): the twin of planes_pair_aligned for one plane of texels
+__device__ __forceinline__ bool plane_pair_aligned_422(const SurfView &p) { return ((((uintptr_t)p.ptr) | p.pitch) & 15u) == 0; }
+
+// The block's store.  The plane's base and pitch are 8-byte aligned (smr_render_layouts routes other planes through smr_rgba_to_frame): a
+// full block is one 8-byte store per row at row * pitch + px0 * 2, the half block of a width with W % 4 == 2 one texel per row.
+// `pair` (wave-uniform, as for store_yuv_block; base and pitch 16-byte aligned): lanes l and l ^ 1 exchange rows — the even lane stores 16
+// bytes of row 0, the odd lane 16 bytes of row 1: two store instructions per lane pair and row instead of four, the same bytes.
+template <int NV>
+__device__ __forceinline__ void store_packed422_block(const u32 (&acc)[8], int px0, int py0, int W, const SurfView &p, bool pair) {
+    float cr[8], cg[8], cb[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        cr[k] = (float)(acc[k] & 0xffu);
+        cg[k] = (float)((acc[k] >> 8) & 0xffu);
+        cb[k] = (float)((acc[k] >> 16) & 0xffu);
+    }
+    u32 yrow0 = 0, yrow1 = 0, uv0 = 0, uv1 = 0;
+    bool flagged = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        bool f0, f1;
+        yrow0 |= yuvfast::convert<0>(cr[k], cg[k], cb[k], &f0) << (8 * k);
+        yrow1 |= yuvfast::convert<0>(cr[4 + k], cg[4 + k], cb[4 + k], &f1) << (8 * k);
+        flagged |= f0 | f1;
+    }
+    // chroma: the tap at the 4:2:2 chroma texel centre = weights (1/2, 1/2) on the pair, a * .5 + b * .5 == (a + b) * .5 bit for bit (a power
+    // of two scales exactly); the fast path takes the pair's byte sums (exact in f32)
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int a = 4 * (q >> 1) + 2 * (q & 1);
+        const float sr = cr[a] + cr[a + 1], sg = cg[a] + cg[a + 1], sb = cb[a] + cb[a + 1];
+        bool f1, f2;
+        const u32 c = (yuvfast::convert422<1>(sr, sg, sb, &f1) << (8 * (q & 1))) | (yuvfast::convert422<2>(sr, sg, sb, &f2) << (16 + 8 * (q & 1)));
+        if (q < 2) uv0 |= c; else uv1 |= c;
+        flagged |= f1 | f2;
+    }
+    if (flagged) {
+        YUV_SLOW_PATH_STAYS_A_BRANCH();
+        yuv_block_repair_422(acc, yrow0, yrow1, uv0, uv1);
+    }
+    const u32 t00 = packed422_texel<NV>(yrow0, uv0, 0), t01 = packed422_texel<NV>(yrow0, uv0, 1);
+    const u32 t10 = packed422_texel<NV>(yrow1, uv1, 0), t11 = packed422_texel<NV>(yrow1, uv1, 1);
+    if (pair) {  // (an interior tile: no half block, px0 = 4 * lane within the row)
+        const bool odd = (px0 & 4) != 0;
+        // the even lane gets its right neighbour's row 0, the odd lane its left neighbour's row 1
+        const u32 n0 = (u32)dev_mov_dpp_quad_swap((int)(odd ? t00 : t10)), n1 = (u32)dev_mov_dpp_quad_swap((int)(odd ? t01 : t11));
+        g_st_u32x4(p.ptr + b_off(py0 + (odd ? 1 : 0), p.pitch, (px0 & ~7) * 2), odd ? make_uint4(n0, n1, t10, t11) : make_uint4(t00, t01, n0, n1));
+        return;
+    }
+    u8 *o = p.ptr + b_off(py0, p.pitch, px0 * 2);
+    if (px0 + 3 >= W) {  // (W is even: the last block of a row holds four or two pixels)
+        g_st_u32(o, t00);
+        g_st_u32(o + p.pitch, t10);
+    } else {
+        g_st_u32x2(o, t00, t01);
+        g_st_u32x2(o + p.pitch, t10, t11);
+    }
+}
+
 // Whether a tile's blocks may be stored by lane pairs (store_yuv_block's `pair`, decided once per tile, wave-uniformly): the tile lies wholly
 // inside the output — every lane of every wave holds a whole 4 x 2 block — and the planes' bases and pitches keep a pair's 8 bytes of Y'
 // and 4 bytes of U / V naturally aligned (the library's own planes always; a wrapped frame with tight rows of odd width does not).
@@ -423,6 +533,7 @@ __device__ __forceinline__ bool planes_pair_aligned(const SurfView &yp, const Su
 #if defined(SMR_EMU) && !defined(SMR_EMU_WAVE_EXCHANGE)
     return false;  // (a harness of the lane emulator that sets up no per-wave exchange — tests/emu/emu_compose.cpp: the per-lane stores everywhere)
 #else
+    if (NV >= 3) return plane_pair_aligned_422(yp);  // (its own predicate: one plane of texels, 16 bytes per lane)
     if (NV == 2) return false;
     bool ok = ((((uintptr_t)yp.ptr) | yp.pitch) & 7u) == 0;
     if (NV == 0) ok = ok && ((((uintptr_t)up.ptr) | up.pitch | ((uintptr_t)vp.ptr) | vp.pitch) & 3u) == 0;
@@ -436,6 +547,10 @@ __device__ __forceinline__ bool planes_pair_aligned(const SurfView &yp, const Su
 template <int NV>
 __device__ __forceinline__ void store_yuv_block(const u32 (&acc)[8], int px0, int py0, int W, const SurfView &yp, const SurfView &up, const SurfView &vp,
                                                 bool pair = false) {
+    if (NV >= 3) {  // a packed 4:2:2 frame's plane (in `yp`)
+        store_packed422_block<NV>(acc, px0, py0, W, yp, pair);
+        return;
+    }
     // (W is even: the last block of a row holds four or two pixels)
     const bool half = px0 + 3 >= W;
     if (NV == 2) {  // an RGBA8 node texture (LayoutNode::render into a NodeTexture): the composited bytes as they are
@@ -545,7 +660,7 @@ __device__ __forceinline__ bool wave_any(bool v) {
 }
 
 // Rows [band, band + rh) of tile `tile`, composited by the whole workgroup (uniform call; may be called again).
-// NV = 0: planar Y,U,V (4:2:0); NV = 1: NV12 (Y + interleaved UV); NV = 2: RGBA8 surface (in `yp`)
+// NV = 0: planar Y,U,V (4:2:0); NV = 1: NV12 (Y + interleaved UV); NV = 2: RGBA8 surface (in `yp`); NV = 3 / 4: packed 4:2:2, UYVY / YUYV (the plane in `yp`)
 // BIG: the layout list is longer than the LDS copy (B_MAX_LAYOUTS / B_MAX_MASKS) and is read where it lies in memory
 // `pre`: the tile's record from k_classify_tiles — touching layers, start layer and tile_needs' bits of the WHOLE tile, valid for every
 // band of it (a layer solid over the tile is solid over the band; a superset of the band's touching layers composites to the same

@@ -62,4 +62,29 @@ YF_FN uint32_t convert(float r, float g, float b, bool *flag) {
     return (uint32_t)x;  // v_cvt_u32_f32: truncation (x lies in [16, 241])
 }
 
+// ---- 4:2:2 (packed UYVY / YUYV outputs): Cb, Cr of a horizontal PAIR of pixels.  The reference's chroma sample sits exactly between the two
+// texels: a * .5 + b * .5 of the byte / 255 values per channel, then the plane formulas.  R, G, B are the pair's byte SUMS (exact in f32: at most
+// 510), the / 2 of the mean is folded into the coefficients.  A guard of its own name: tools/check_yuv_fast_422.cpp enumerates the complete
+// domain — 511^3 sums times every f32 value the mean can take for a sum — with THIS header, and would widen this constant, never DELTA.
+constexpr double DELTA422 = 1.0 / 8192.0;  // (2^-13 suffices: 2.67 x the largest deviation over the complete domain, 4.58e-5 — profiles/yuv_fast_422_check.txt)
+
+// planes 1, 2: Cb, Cr from a pixel pair's byte sums
+constexpr K constants422(int plane) {
+    const double c16 = (double)(16.0f / 255.0f);
+    const double kc = (double)0.87843137254f;
+    const double cr = plane == 1 ? (double)-0.1146f : 0.5;
+    const double cg = plane == 1 ? (double)-0.3854f : (double)-0.4542f;
+    const double cb = plane == 1 ? 0.5 : (double)-0.0458f;
+    return K{(float)(cr * kc / 2.0), (float)(cg * kc / 2.0), (float)(cb * kc / 2.0), (float)((0.5 * kc + c16) * 255.0 + 0.5 + DELTA422)};
+}
+
+template <int PLANE>
+YF_FN uint32_t convert422(float r, float g, float b, bool *flag) {
+    static_assert(PLANE == 1 || PLANE == 2, "luma is convert<0> of the pixel's bytes");
+    constexpr K k = constants422(PLANE);
+    const float x = __builtin_fmaf(r, k.kr, __builtin_fmaf(g, k.kg, __builtin_fmaf(b, k.kb, k.k0)));
+    *flag = fract(x) < (float)(2.0 * DELTA422);
+    return (uint32_t)x;
+}
+
 }  // namespace yuvfast

@@ -209,6 +209,9 @@ class Renderer:
 
     # -- scenes (state.rs:177-189)
     def update_scene(self, output_id: str, width: int, height: int, scene: Union[str, dict], output_format: int = FRAME_PLANAR_YUV420) -> List[Node]:
+        """`output_format`: FRAME_PLANAR_YUV420 / _YUV422 / _YUV444, FRAME_NV12, FRAME_RGBA, or packed 4:2:2 — FRAME_UYVY422 / FRAME_YUYV422, one
+        plane of (width / 2) x height texels, an even `width` only.  Outputs are 8-bit, BT.709, limited range; a refused update leaves the
+        output's previous scene active."""
         text = scene if isinstance(scene, str) else json.dumps(scene)
         svg_errors = getattr(self, "_svg_errors", {})
         svg_errors.clear()
